@@ -2,6 +2,12 @@
 """Benchmark contract (DESIGN.md §5 Measurement).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cami-medium|screen]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the result line.  --dump-outputs DIR
+also writes what the last timed step returned as DIR/<name>.npy (dump_outputs).  --full adds
+the legs that take runs of their own after the timed steps: the checked CPU baseline
+(`cpu_baseline`) and the predicted N-rank shard balance (`config.predicted_imbalance`).
 
 One step = one pass of the HYMET hot path over one input, in the SURVEY.md §8(d) window:
 sketch DB files (.msh) parsed and their HBM tables built, detailed_taxonomy.tsv +
@@ -157,6 +163,70 @@ def cpu_info():
     except OSError:
         pass
     return model, os.cpu_count() or 0
+
+
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_PAF_LINES = 200_000   # PAF lines sampled into paf_sample.npy (14 float64 each: 22 MB)
+
+
+def _crc(b) -> float:
+    """CRC-32 of a text field: exact in a float64, so text compares as a number."""
+    import zlib
+    return float(zlib.crc32(b))
+
+
+def _line_starts(buf):
+    """(start offsets, end offsets) of the newline-terminated lines of a bytes-like text."""
+    a = np.frombuffer(buf, np.uint8)
+    ends = [np.flatnonzero(a[o:o + (1 << 26)] == 10) + o for o in range(0, len(a), 1 << 26)]
+    ends = np.concatenate(ends) if ends else np.zeros(0, np.int64)
+    return np.r_[0, ends[:-1] + 1].astype(np.int64)[:len(ends)], ends
+
+
+def dump_outputs(out_dir, screen=None, res=None):
+    """--dump-outputs DIR: what the last timed step returned to its caller, as float64 arrays
+    (rank 0's view; the inputs are seeded, so two builds run with the same arguments can be
+    compared array for array).  Text fields are stored as their CRC-32.
+
+    screen<d>_shared / screen<d>_median  per reference of sketch DB d (ScreenResult)
+    screen_sizes                          per DB: set_size, n_kmers
+    selected                              CRC-32 of each selected candidate's name, in order
+    tsv                                   per classified_sequences.tsv row: CRC-32 of the query
+                                          name, of the lineage, of the level; the confidence
+    paf_sample                            per sampled PAF line (every line up to DUMP_PAF_LINES,
+                                          else a fixed seeded sample, in file order): line index,
+                                          CRC-32 of the query name, qlen, qstart, qend, strand
+                                          (+1 / -1), CRC-32 of the target name, tlen, tstart,
+                                          tend, matches, block length, mapq, CRC-32 of the tags
+    summary                               TSV rows, classified rows, PAF lines, TSV bytes,
+                                          CRC-32 of the TSV, PAF bytes, CRC-32 of the PAF text"""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+    for d, r in enumerate(screen or []):
+        save(f"screen{d}_shared", r.shared)
+        save(f"screen{d}_median", r.median)
+    save("screen_sizes", [[r.set_size, r.n_kmers] for r in screen or []])
+    if res is None:
+        return
+    save("selected", [_crc(n.encode()) for n in res.selected])
+    rows = [r.split(b"\t") for r in res.tsv.splitlines()[1:] if r]
+    save("tsv", np.array([[_crc(r[0]), _crc(r[1]), _crc(r[2]), float(r[3])] for r in rows], np.float64).reshape(-1, 4))
+    t = res.paf_text
+    paf = t.view() if hasattr(t, "view") else memoryview(t or b"")
+    starts, ends = _line_starts(paf)
+    pick = np.arange(len(starts))
+    if len(pick) > DUMP_PAF_LINES:
+        pick = np.sort(np.random.default_rng(2024).choice(len(pick), DUMP_PAF_LINES, replace=False))
+    out = np.zeros((len(pick), 14), np.float64)
+    for j, i in enumerate(pick):
+        f = bytes(paf[starts[i]:ends[i]]).split(b"\t", 12)
+        out[j] = [i, _crc(f[0]), int(f[1]), int(f[2]), int(f[3]), 1.0 if f[4] == b"+" else -1.0, _crc(f[5]),
+                  int(f[6]), int(f[7]), int(f[8]), int(f[9]), int(f[10]), int(f[11]), _crc(f[12]) if len(f) > 12 else 0.0]
+    save("paf_sample", out)
+    save("summary", [res.n_queries, res.n_classified, res.n_paf_lines, len(res.tsv), _crc(res.tsv), len(paf), _crc(paf)])
 
 
 # ------------------------------------------------------------------ CAMI-medium
@@ -358,18 +428,22 @@ def bench_cami(args, comm, gpu, torch):
         "roofline": roofline_from_prof(prof, workload=args.workload, batch_mbp=args.batch_mbp),
         "path_roofline": path_roofline(prof, args.steps, step, total_bases, total_bases, n_lines, len(ix.parts), comm.world),
     }
-    if comm.world == 1:
+    if comm.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res.screen, res)
+    if args.full and comm.world == 1:
         try:
             out["config"]["predicted_imbalance"] = shard_balance(gpu, pipe, fasta)
         except Exception as e:  # informative only
             out["config"]["predicted_imbalance"] = {"error": repr(e)}
-    if comm.rank == 0 and comm.world == 1 and not args.no_cpu:   # the CPU leg runs at N=1 only
+    if args.full and comm.rank == 0 and comm.world == 1 and not args.no_cpu:   # the CPU leg runs at N=1 only
         try:
             out["cpu_baseline"] = cpu_baseline_cami(args, pipe, res, fasta, db, tax, hier)
         except Exception as e:  # the baseline is informative; never lose the GPU line
             import traceback
             traceback.print_exc()
             out["cpu_baseline"] = {"error": repr(e)}
+    import shutil
+    shutil.rmtree(td, ignore_errors=True)   # the .msh and taxonomy files of this run
     return out
 
 
@@ -730,13 +804,15 @@ def bench_screen(args, comm, gpu, torch):
     comm.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        scr.screen(gpu, pool, [db], [table], comm)
+        last = scr.screen(gpu, pool, [db], [table], comm)
     torch.cuda.synchronize()
     comm.barrier()
     dt = comm.max_float(time.perf_counter() - t0)
     gpu.prof(False)
     prof = gpu.prof_table()
     step = dt / args.steps
+    if comm.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     return {"metric": "contigs/s screened (C2 Zymo-shaped pool vs sketch1-sized DB)", "value": comm.world * ss.n / step,
             "unit": "contigs/s", "n_gpus": comm.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
@@ -824,7 +900,11 @@ def parse_args(argv=None):
     ap.add_argument("--screen-refs", type=int, default=100_000, help="screen-only workload: references in the DB")
     ap.add_argument("--db-hashes", default=None, help="hashes per sketch DB, comma-separated (C4: 1e8; C5: 1e8,5e7,1e7)")
     ap.add_argument("--cand-max", type=int, default=5000, help="CAND_MAX (run_hymet_cami.sh:26)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checked CPU baseline and the predicted shard balance")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU baseline threads (default: every CPU the scheduler affinity and cgroup quota give this job)")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU mapping in the checked CPU leg")
@@ -838,6 +918,8 @@ def parse_args(argv=None):
                     help="run rank R of an N-rank job alone on this GPU, collectives replaced by stand-ins "
                          "(bench_emulate: a predicted N-GPU step, not a measurement)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # CAMI-high (C5, BASELINE.json configs[4]): 14 taxa (tools/generate_cami_subsets.py:343),
     # the full CAND_MAX of 5000 candidates (~20 Gbp, ten -I2g parts), ~2 Gbp of contigs,
     # three sketch DBs of 1e8 / 5e7 / 1e7 hashes

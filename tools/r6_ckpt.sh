@@ -9,4 +9,4 @@ mkdir -p $OUT
 HB=$!
 trap "kill $HB" EXIT
 timeout -k 10 900 python3 bench.py --emulate-rank 0,7/8 --steps 3 --warmup 2 > $OUT/emulate_c4.json 2> $OUT/emulate_c4.err || exit $?
-timeout -k 10 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
