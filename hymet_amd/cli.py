@@ -22,6 +22,9 @@
         == scripts/downloadDB.py:178-249 offline (detailed_taxonomy.tsv, combined_genomes.fasta)
     python -m hymet_amd.cli eval-cami [--pred-profile ... --outdir D]
         == tools/eval_cami.py (CAMI profile and contig metrics)
+    python -m hymet_amd.cli sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] -o PREFIX FILE...
+        == mash sketch (builds the sketch DB the screen reads; the reference downloads its DBs,
+           so there is no stage script and no scripts/ wrapper for it)
 
 The thin wrappers under scripts/ call these, so run_hymet_cami.sh / main.pl can use them
 in place of the reference stage scripts unchanged.  All device work goes through
@@ -298,6 +301,83 @@ def cmd_download_db(argv: Sequence[str]) -> int:
     return 0
 
 
+# ------------------------------------------------------------------ sketch (mash sketch)
+SKETCH_USAGE = "usage: sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] -o PREFIX FILE..."
+
+
+def sketch_args(argv: Sequence[str]):
+    """`mash sketch`'s flag letters.  Returns the parsed namespace, or None after printing the
+    usage line (unknown flag, -n, no -o, no FILE)."""
+    class _Parser(argparse.ArgumentParser):
+        def error(self, message):
+            raise ValueError(message)
+
+    p = _Parser(prog="sketch", add_help=False, allow_abbrev=False)
+    p.add_argument("-k", type=int, default=21, dest="k")
+    p.add_argument("-s", type=int, default=1000, dest="s")
+    p.add_argument("-S", type=int, default=42, dest="seed")
+    p.add_argument("-i", action="store_true", dest="individual")
+    p.add_argument("-Z", action="store_true", dest="preserve_case")
+    p.add_argument("-l", action="store_true", dest="lists")
+    p.add_argument("-n", action="store_true", dest="noncanonical")
+    p.add_argument("-o", dest="out")
+    p.add_argument("-h", action="store_true", dest="help")
+    p.add_argument("files", nargs="*")
+    try:
+        a = p.parse_args(list(argv))
+        if a.help:
+            print(cmd_sketch.__doc__, file=sys.stderr)
+            raise ValueError("")
+        if a.noncanonical:
+            raise ValueError("-n: noncanonical sketches are not supported")
+        if not a.out:
+            raise ValueError("-o PREFIX is required")
+        if not a.files:
+            raise ValueError("no input FILE")
+    except ValueError as e:
+        if str(e):
+            print(f"sketch: {e}", file=sys.stderr)
+        print(SKETCH_USAGE, file=sys.stderr)
+        return None
+    return a
+
+
+def expand_lists(files: Sequence[str]) -> List[str]:
+    """-l: each FILE is a list of paths, one per line (blank lines skipped)."""
+    out: List[str] = []
+    for lf in files:
+        with open(lf, "r", encoding="utf-8") as f:
+            out.extend(l.strip() for l in f if l.strip())
+    return out
+
+
+def cmd_sketch(argv: Sequence[str]) -> int:
+    """mash sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] -o PREFIX FILE...: sketch each FILE
+    (each record with -i) on the GPU and write PREFIX.msh (the suffix is not doubled).
+      -k  k-mer size, 1..32 (21)        -s  sketch size (1000)       -S  hash seed (42)
+      -i  one reference per sequence    -Z  preserve case            -l  FILEs list paths
+    Known limits: -n (noncanonical), protein alphabets and read options (-r, -m) are not
+    supported, and hash lists are always written 64 bits wide, also for k <= 16 where Mash
+    writes 32-bit lists (this project's reader widens either form)."""
+    a = sketch_args(argv)
+    if a is None:
+        return 2
+    from . import sketch as sk
+    from ._lib import Gpu
+    from .msh import write_msh
+    files = expand_lists(a.files) if a.lists else list(a.files)
+    out = a.out if a.out.endswith(".msh") else a.out + ".msh"
+    gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
+    print("Sketching...", file=sys.stderr)
+    db = sk.sketch_files(gpu, files, k=a.k, seed=a.seed, s=a.s, individual=a.individual, preserve_case=a.preserve_case)
+    if db.n_refs == 0:
+        print("ERROR: no sequences to sketch.", file=sys.stderr)
+        return 1
+    print(f"Writing to {out}...", file=sys.stderr)
+    write_msh(db, out)
+    return 0
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv:
@@ -329,6 +409,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if cmd == "eval-cami":
         from .evaluate import main as eval_main
         return eval_main(rest)
+    if cmd == "sketch":
+        return cmd_sketch(rest)
     print(f"unknown subcommand {cmd!r}", file=sys.stderr)
     return 2
 

@@ -28,8 +28,11 @@
 // Roofline: HBM/latency bound (random 8-B key probes); algorithmic bytes per k-mer are
 // 0.375 (packed read) + 8 per DB probe (+4 per hit), DESIGN.md §Screen.
 #include "common.hpp"
+#include "mash_hash.hpp"
 
 namespace {
+
+using namespace hymet::mash;
 
 constexpr uint64_t kEmpty = ~0ull;
 
@@ -47,78 +50,6 @@ __device__ __forceinline__ uint64_t home_slot(uint64_t h, int shift) { return (h
 #endif
 constexpr int kTile = HYMET_SCREEN_TILE;  // k-mer start positions per thread (multiple of 32: lanes stay in phase)
 constexpr int kMaxDb = 4;
-
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdULL;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ULL;
-    k ^= k >> 33;
-    return k;
-}
-
-// MurmurHash3_x64_128 word 0 of a K-byte key held little-endian in w[0..3].
-template <int K>
-__device__ __forceinline__ uint64_t murmur3_h0(const uint64_t (&w)[4], uint32_t seed) {
-    constexpr uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
-    constexpr int NB = K / 16, TAIL = K & 15;
-    uint64_t h1 = seed, h2 = seed;
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        uint64_t k1 = w[2 * b], k2 = w[2 * b + 1];
-        k1 *= c1; k1 = rotl64(k1, 31); k1 *= c2; h1 ^= k1;
-        h1 = rotl64(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
-        k2 *= c2; k2 = rotl64(k2, 33); k2 *= c1; h2 ^= k2;
-        h2 = rotl64(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
-    }
-    if constexpr (TAIL > 8) {
-        uint64_t k2 = w[2 * NB + 1];
-        k2 *= c2; k2 = rotl64(k2, 33); k2 *= c1; h2 ^= k2;
-    }
-    if constexpr (TAIL > 0) {
-        uint64_t k1 = w[2 * NB];
-        k1 *= c1; k1 = rotl64(k1, 31); k1 *= c2; h1 ^= k1;
-    }
-    h1 ^= (uint64_t)K;
-    h2 ^= (uint64_t)K;
-    h1 += h2;
-    h2 += h1;
-    h1 = fmix64(h1);
-    h2 = fmix64(h2);
-    return h1 + h2;
-}
-
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// MurmurHash3_x86_32 of a K-byte key (K <= 16) held little-endian in w[0..1], bytes past K zero.
-template <int K>
-__device__ __forceinline__ uint32_t murmur3_x86_32(const uint64_t (&w)[4], uint32_t seed) {
-    constexpr uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
-    constexpr int NB = K / 4, TAIL = K & 3;
-    uint32_t h1 = seed;
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        uint32_t k1 = (uint32_t)(w[b >> 1] >> (32 * (b & 1)));
-        k1 *= c1; k1 = rotl32(k1, 15); k1 *= c2;
-        h1 ^= k1; h1 = rotl32(h1, 13); h1 = h1 * 5 + 0xe6546b64u;
-    }
-    if constexpr (TAIL > 0) {
-        uint32_t k1 = (uint32_t)(w[NB >> 1] >> (32 * (NB & 1)));  // the K & 3 tail bytes, zero above
-        k1 *= c1; k1 = rotl32(k1, 15); k1 *= c2; h1 ^= k1;
-    }
-    h1 ^= (uint32_t)K;
-    h1 ^= h1 >> 16; h1 *= 0x85ebca6bu;
-    h1 ^= h1 >> 13; h1 *= 0xc2b2ae35u;
-    h1 ^= h1 >> 16;
-    return h1;
-}
-
-template <int K>
-__device__ __forceinline__ uint64_t mash_hash(const uint64_t (&w)[4], uint32_t seed) {
-    if constexpr (K <= 16) return (uint64_t)murmur3_x86_32<K>(w, seed);
-    else return murmur3_h0<K>(w, seed);
-}
 
 struct CountParams {
     const uint32_t *w2b;
@@ -139,15 +70,9 @@ struct CountParams {
     unsigned long long *nkmers;
 };
 
-__device__ __forceinline__ uint32_t ascii_of(uint32_t c) { return (0x54474341u >> (8 * c)) & 0xFFu; }
-
 template <int K>
 __global__ __launch_bounds__(256) void screen_count_kernel(CountParams P) {
     constexpr bool LO = K <= 16;  // 32-bit sketches: tables built with key_bits 32
-    constexpr int NW = (K + 7) / 8;
-    constexpr int TOPB = K - 8 * (NW - 1);
-    constexpr uint64_t TOPMASK = TOPB == 8 ? ~0ull : ((1ull << (8 * TOPB)) - 1);
-    constexpr uint64_t KMASK = K == 32 ? ~0ull : ((1ull << (2 * K)) - 1);
     const int64_t n_pos = P.pos_end - P.pos_begin;
     const int64_t n_tiles = (n_pos + kTile - 1) / kTile;
     uint64_t nk = 0;
@@ -156,8 +81,7 @@ __global__ __launch_bounds__(256) void screen_count_kernel(CountParams P) {
         const int64_t p0 = P.pos_begin + tile * kTile;                 // first k-mer start
         const int64_t p1 = min(p0 + kTile, P.pos_end);                 // one past last start
         const int64_t iend = min(p1 + K - 1, P.n_bases);                // bases to read: [p0, iend)
-        uint64_t fwd = 0, rc = 0;
-        uint64_t F[4] = {0, 0, 0, 0}, R[4] = {0, 0, 0, 0};
+        KmerRoll<K> roll;
         int run = 0;
         uint32_t cw = 0, mw = 0;
         for (int64_t i = p0; i < iend; i++) {
@@ -166,19 +90,11 @@ __global__ __launch_bounds__(256) void screen_count_kernel(CountParams P) {
             const uint32_t c = (cw >> (2 * (i & 15))) & 3u;
             const uint32_t bad = (mw >> (i & 31)) & 1u;
             run = bad ? 0 : run + 1;
-            fwd = ((fwd << 2) | c) & KMASK;
-            rc = (rc >> 2) | ((uint64_t)(3u - c) << (2 * (K - 1)));
-#pragma unroll
-            for (int j = 0; j < NW - 1; j++) F[j] = (F[j] >> 8) | (F[j + 1] << 56);
-            F[NW - 1] = (F[NW - 1] >> 8) | ((uint64_t)ascii_of(c) << (8 * (TOPB - 1)));
-#pragma unroll
-            for (int j = NW - 1; j > 0; j--) R[j] = (R[j] << 8) | (R[j - 1] >> 56);
-            R[0] = (R[0] << 8) | ascii_of(3u - c);
-            R[NW - 1] &= TOPMASK;
+            roll.push(c);
             if (run < K) continue;                                       // invalid base inside the k-mer
             const int64_t p = i - (K - 1);
             if (p < p0) continue;                                        // warm-up only
-            const uint64_t h = (rc < fwd) ? mash_hash<K>(R, P.seed) : mash_hash<K>(F, P.seed);
+            const uint64_t h = roll.hash(P.seed);
             nk++;
             if (h < P.cand_thr) {
                 unsigned long long idx = atomicAdd(P.cand_n, 1ull);

@@ -1,0 +1,219 @@
+"""Sketch stage: the MI355X replacement for `mash sketch`, the step that builds the sketch
+databases (`data/sketch{1,2,3}.msh`) the screen reads.  The reference workflow downloads
+them; here they are built from genome FASTA files already on disk.
+
+Device work (libhymet_gpu.so, csrc/sketch.hip): one call of `hymet_sketch_batch` sketches a
+whole batch of references exactly -- every canonical k-mer of the packed pool is hashed once
+(the screen's hashing) and the bottom-s distinct hashes of each reference are selected in
+LDS.  Host work here: the chunk plan (which k-mer start positions belong to which
+reference), FASTA reading in batches bounded by bases, and the references' metadata.
+
+The metadata rules (name / comment / length of a reference, below) restate what Mash's
+`sketch` writes from memory of its behaviour.  No Mash binary and no Mash-written .msh is
+available to check them against: they are PARITY-UNPINNED, like the .msh schema (msh.py).
+The hashes are pinned to the CPU oracle (oracle/mash_oracle.c oracle_sketch), as the
+screen is pinned to oracle_screen.
+"""
+from __future__ import annotations
+
+import ctypes
+import sys
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ._lib import load, ptr
+from .msh import SketchDB
+
+# k-mer start positions per chunk (= per workgroup).  Chosen among 256 k, 1 M and 4 M by
+# tools/sketch_bench.py
+DEFAULT_CHUNK_BASES = 1 << 20
+# bases per batch of sketch_files: the ASCII pool on the host and in HBM, then 0.375 B per base
+DEFAULT_BATCH_BASES = 1 << 29
+# output rows per batch of sketch_files are capped so that rows x s x 8 B stays under this
+_MAX_OUT_BYTES = 1 << 30
+
+
+def plan_chunks(starts, lengths, group_of, k: int, chunk_bases: int):
+    """The work plan of hymet_sketch_batch: (chunk_sketch int32, chunk_begin int64, chunk_end
+    int64), sorted by sketch id.  starts / lengths: the records' offsets and lengths in the
+    pool (SeqSet.starts / .lengths); group_of[i]: the sketch record i belongs to.  The records
+    of a group must be contiguous in the pool (ValueError otherwise).
+
+    Records shorter than k are skipped.  A group's span runs from the first k-mer start of its
+    first usable record to one past the last k-mer start of its last usable one, and is cut
+    into ceil(span / chunk_bases) chunks of equal size (the last may be shorter).  A chunk
+    never crosses a group.  Every k-mer start of every record of length >= k is covered exactly
+    once; positions in separators, in short records between usable ones and in the k - 1 tail
+    of a record are covered too: their k-mers hold a separator, so the kernel drops them."""
+    starts = np.asarray(starts, np.int64)
+    lengths = np.asarray(lengths, np.int64)
+    group_of = np.asarray(group_of, np.int64)
+    if not (len(starts) == len(lengths) == len(group_of)):
+        raise ValueError("plan_chunks: starts, lengths and group_of differ in length")
+    if k < 1 or chunk_bases < 1:
+        raise ValueError("plan_chunks: k and chunk_bases must be positive")
+    empty = (np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64))
+    if len(group_of) == 0:
+        return empty
+    if group_of.min() < 0:
+        raise ValueError("plan_chunks: negative group id")
+    # runs of equal group id; a group seen in two runs is not contiguous
+    run_first = np.flatnonzero(np.r_[True, group_of[1:] != group_of[:-1]])
+    run_gid = group_of[run_first]
+    if len(np.unique(run_gid)) != len(run_gid):
+        raise ValueError("plan_chunks: the records of a group are not contiguous in the pool")
+    if len(starts) > 1 and (np.diff(starts) < 0).any():
+        raise ValueError("plan_chunks: record starts are not ascending")
+    usable = np.flatnonzero(lengths >= k)
+    if len(usable) == 0:
+        return empty
+    g = group_of[usable]
+    first = np.flatnonzero(np.r_[True, g[1:] != g[:-1]])          # first usable record of each group
+    last = np.r_[first[1:] - 1, len(g) - 1]
+    gid = g[first]
+    b = starts[usable[first]]
+    e = starts[usable[last]] + lengths[usable[last]] - k + 1
+    span = e - b
+    n = -(-span // int(chunk_bases))
+    size = -(-span // n)
+    which = np.repeat(np.arange(len(gid)), n)                     # chunk -> group slot
+    j = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)  # chunk index within its group
+    cb = b[which] + j * size[which]
+    ce = np.minimum(cb + size[which], e[which])
+    keep = cb < ce     # ceil(span / size) can be below n: drop the empty tail chunks
+    cs, cb, ce = gid[which][keep], cb[keep], ce[keep]
+    order = np.argsort(cs, kind="stable")
+    return cs[order].astype(np.int32), cb[order].astype(np.int64), ce[order].astype(np.int64)
+
+
+def max_sketch_size() -> int:
+    return int(load().hymet_sketch_max_size())
+
+
+def sketch_pool(gpu, pool, group_of=None, k: int = 21, seed: int = 42, s: int = 1000,
+                chunk_bases: Optional[int] = None) -> List[np.ndarray]:
+    """Mash `sketch` of a packed pool (seqio.DevicePool): the bottom-s distinct canonical k-mer
+    hashes of every group of records, sorted, as np.uint64 arrays -- one per group id in
+    0..max(group_of).  group_of=None: one sketch per record (`mash sketch -i`).  One call of
+    hymet_sketch_batch and one copy to the host, whatever the number of groups."""
+    torch = gpu.torch
+    ss = pool.ss
+    if group_of is None:
+        group_of = np.arange(ss.n, dtype=np.int64)
+    group_of = np.asarray(group_of, np.int64)
+    if len(group_of) != ss.n:
+        raise ValueError("sketch_pool: group_of needs one entry per record")
+    n_sk = int(group_of.max()) + 1 if len(group_of) else 0
+    if n_sk == 0:
+        return []
+    s = int(s)
+    cs, cb, ce = plan_chunks(ss.starts, ss.lengths, group_of, k, int(chunk_bases or DEFAULT_CHUNK_BASES))
+    # rows and, behind them in the same buffer, the rows' counts: one copy brings both
+    out = gpu.empty(n_sk * s + (n_sk + 1) // 2, torch.int64)
+    d_n = ctypes.c_void_p(out.data_ptr() + 8 * n_sk * s)
+    gpu.call("hymet_sketch_batch", ptr(pool.w2b), ptr(pool.wmask), pool.n_bases, int(k), int(seed), s, len(cs),
+             cs.ctypes.data_as(ctypes.c_void_p), cb.ctypes.data_as(ctypes.c_void_p), ce.ctypes.data_as(ctypes.c_void_p),
+             n_sk, ptr(out), d_n)
+    host = out.cpu().numpy()
+    rows = host[:n_sk * s].view(np.uint64).reshape(n_sk, s)
+    cnt = host[n_sk * s:].view(np.int32)[:n_sk]
+    return [rows[r, :c] for r, c in enumerate(cnt.tolist())]    # views of the one host copy
+
+
+# ------------------------------------------------------------------ metadata (unpinned)
+def _join(name: str, comment: str) -> str:
+    return f"{name} {comment}" if comment else name
+
+
+def file_meta(path: str, names: Sequence[str], comments: Sequence[str], lengths: Sequence[int],
+              k: int) -> Optional[Tuple[str, str, int]]:
+    """(name, comment, length) of the reference `mash sketch` makes of one FASTA file, or None
+    when no record has k bases (the file is skipped).  name = the path as given; length = the
+    summed lengths of the records of >= k bases; comment = "<first name> <first comment>" for
+    one such record, "[N seqs] <first name> <first comment> [...]" for N > 1.  Unpinned (module
+    docstring)."""
+    ok = [i for i, L in enumerate(lengths) if int(L) >= k]
+    if not ok:
+        return None
+    head = _join(names[ok[0]], comments[ok[0]])
+    comment = head if len(ok) == 1 else f"[{len(ok)} seqs] {head} [...]"
+    return str(path), comment, int(sum(int(lengths[i]) for i in ok))
+
+
+def _warn(msg: str):
+    print(f"WARNING: {msg}", file=sys.stderr)
+
+
+def sketch_files(gpu, paths: Sequence[str], k: int = 21, seed: int = 42, s: int = 1000, individual: bool = False,
+                 preserve_case: bool = False, batch_bases: int = DEFAULT_BATCH_BASES,
+                 chunk_bases: Optional[int] = None) -> SketchDB:
+    """`mash sketch [-i] [-Z] -k K -s S -S SEED FILE...` -> SketchDB, references in argument
+    order.  The files are read (gzip too, seqio) and sketched in batches of about batch_bases
+    bases -- read, pack (DevicePool), sketch_pool -- so neither the host nor HBM ever holds the
+    whole collection; one file is the smallest unit of a batch.
+
+    File mode: one reference per file (file_meta); a file with no record of k bases is skipped
+    with a warning.  individual (`-i`): one reference per record, named and commented as the
+    record; shorter records are skipped with a warning.  preserve_case (`-Z`): lower-case bases
+    are not k-mer letters.  Metadata rules unpinned (module docstring)."""
+    from .seqio import DevicePool, from_records, read_fasta
+    if not 1 <= int(k) <= 32:
+        raise ValueError(f"k={k}: Mash k-mer sizes are 1..32")
+    if not 1 <= int(s) <= max_sketch_size():
+        raise ValueError(f"sketch size {s}: supported sizes are 1..{max_sketch_size()}")
+    alpha = DevicePool.ALPHA_MASH_PRESERVE_CASE if preserve_case else DevicePool.ALPHA_MASH
+    max_refs = max(1, _MAX_OUT_BYTES // (8 * int(s)))
+    names: List[str] = []
+    comments: List[str] = []
+    lengths: List[int] = []
+    hashes: List[np.ndarray] = []
+    recs, group_of, meta = [], [], []     # the batch being collected
+    bases = 0
+
+    def flush():
+        nonlocal recs, group_of, meta, bases
+        if meta:
+            pool = DevicePool(gpu, from_records(recs), alpha)
+            rows = sketch_pool(gpu, pool, np.asarray(group_of, np.int64), k, seed, s, chunk_bases)
+            del pool
+            for (nm, cm, ln), h in zip(meta, rows):
+                names.append(nm)
+                comments.append(cm)
+                lengths.append(ln)
+                hashes.append(h)
+        recs, group_of, meta, bases = [], [], [], 0
+
+    for p in paths:
+        ss = read_fasta([p])
+        if individual:
+            for i in range(ss.n):
+                L = int(ss.lengths[i])
+                if L < k:
+                    _warn(f"Skipping sequence {ss.names[i]!r} of {p}: shorter than the k-mer size ({L} < {k}).")
+                    continue
+                if bases and (bases + L > batch_bases or len(meta) >= max_refs):
+                    flush()
+                group_of.append(len(meta))
+                meta.append((ss.names[i], ss.comments[i], L))
+                recs.append((ss.names[i], ss.comments[i], ss.seq(i)))
+                bases += L
+            continue
+        m = file_meta(str(p), ss.names, ss.comments, ss.lengths, k)
+        if m is None:
+            _warn(f"Skipping {p}: no sequence of at least {k} bases.")
+            continue
+        if bases and (bases + ss.total_bases > batch_bases or len(meta) >= max_refs):
+            flush()
+        for i in range(ss.n):
+            group_of.append(len(meta))
+            recs.append((ss.names[i], ss.comments[i], ss.seq(i)))
+        meta.append(m)
+        bases += ss.total_bases
+    flush()
+    off = np.zeros(len(hashes) + 1, np.int64)
+    if hashes:
+        off[1:] = np.cumsum([len(h) for h in hashes])
+    return SketchDB(k=int(k), seed=int(seed), sketch_size=int(s), alphabet="ACGT", preserve_case=bool(preserve_case),
+                    noncanonical=False, names=names, comments=comments, lengths=np.asarray(lengths, np.int64),
+                    offsets=off, hashes=np.concatenate(hashes) if hashes else np.zeros(0, np.uint64))

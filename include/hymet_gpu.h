@@ -204,6 +204,27 @@ int hymet_screen_stats(hymet_ctx *ctx, const int64_t *d_ref_off, int64_t n_refs,
                        const int32_t *d_canon_of, const uint32_t *d_counts, uint32_t *d_shared,
                        uint32_t *d_median);
 
+/* ------------------------------------------------------------ Mash sketch (DB build)
+ * Replaces `mash sketch` for building the sketch DBs the screen reads (the reference workflow
+ * downloads them): the bottom-s distinct canonical k-mer hashes of each reference, hashed as
+ * hymet_screen_count hashes them (same k range, seed, strand rule and invalid-base handling).
+ * The largest sketch size the kernels' LDS layout holds. */
+int64_t hymet_sketch_max_size(void);
+/* Sketch a batch of references of one packed pool.  The work is planned on the host as chunks:
+ * chunk c covers the k-mer START positions [h_chunk_begin[c], h_chunk_end[c]) of the pool and
+ * belongs to sketch h_chunk_sketch[c]; it may span several records of that sketch (the pool's
+ * separators invalidate the k-mers that cross records).  The chunks are sorted by sketch id
+ * (non-decreasing), do not overlap and lie inside [0, n_bases - k + 1); a plan that breaks any
+ * of this is rejected with HYMET_E_ARG before anything is launched.  s in 1..
+ * hymet_sketch_max_size.  d_out: n_sketches x s uint64; the first d_out_n[r] entries of row r
+ * are sketch r, distinct and ascending; d_out_n[r] = 0 for a sketch with no chunk or no valid
+ * k-mer.  The result does not depend on how the references were cut into chunks.  Everything
+ * is queued on the context's stream; n_chunks == 0 or n_sketches == 0 is not an error. */
+int hymet_sketch_batch(hymet_ctx *ctx, const uint32_t *d_2b, const uint32_t *d_mask, int64_t n_bases,
+                       int k, uint32_t seed, int32_t s, int64_t n_chunks, const int32_t *h_chunk_sketch,
+                       const int64_t *h_chunk_begin, const int64_t *h_chunk_end, int32_t n_sketches,
+                       uint64_t *d_out, int32_t *d_out_n);
+
 /* --------------------------------------------------- minimizer index (minimap2 -d)
  * Replaces `minimap2 -I2g -d reference.mmi combined_genomes.fasta` (scripts/minimap2.sh:12):
  * default indexing parameters k=15, w=10 (no -x at build time), one handle per -I part.
