@@ -54,6 +54,10 @@ _SIGS = {
     "hymet_screen_stats": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "hymet_sketch_max_size": (_i64, []),
     "hymet_sketch_batch": (_i32, [_vp, _vp, _vp, _i64, _i32, _u32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "hymet_mash_dist": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "hymet_mash_dist_tile": (_i32, [_i32]),
+    "hymet_mash_dist_tune": (_i32, [_i32, _i32]),
+    "hymet_mash_dist_select": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _c.POINTER(_i64)]),
     "hymet_mm_sketch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _c.POINTER(_i64)]),
     "hymet_mm_index_build": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(_vp)]),
     "hymet_mm_index_destroy": (_i32, [_vp]),

@@ -25,6 +25,9 @@
     python -m hymet_amd.cli sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] -o PREFIX FILE...
         == mash sketch (builds the sketch DB the screen reads; the reference downloads its DBs,
            so there is no stage script and no scripts/ wrapper for it)
+    python -m hymet_amd.cli dist [-d D] [-v P] [-t] [-i] [-l] REF.msh QUERY...
+        == mash dist (all-pairs distances between sketch DBs; QUERY is .msh or FASTA; like
+           sketch, not a stage of the reference workflow)
 
 The thin wrappers under scripts/ call these, so run_hymet_cami.sh / main.pl can use them
 in place of the reference stage scripts unchanged.  All device work goes through
@@ -378,6 +381,99 @@ def cmd_sketch(argv: Sequence[str]) -> int:
     return 0
 
 
+# ------------------------------------------------------------------ dist (mash dist)
+DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [-i] [-l] REF.msh QUERY..."
+
+
+def dist_args(argv: Sequence[str]):
+    """`mash dist`'s flag letters.  Returns the parsed namespace, or None after printing the
+    usage line (unknown flag, no REF.msh, no QUERY)."""
+    class _Parser(argparse.ArgumentParser):
+        def error(self, message):
+            raise ValueError(message)
+
+    p = _Parser(prog="dist", add_help=False, allow_abbrev=False)
+    p.add_argument("-d", type=float, default=1.0, dest="max_dist")
+    p.add_argument("-v", type=float, default=1.0, dest="max_p")
+    p.add_argument("-t", action="store_true", dest="table")
+    p.add_argument("-i", action="store_true", dest="individual")
+    p.add_argument("-l", action="store_true", dest="lists")
+    p.add_argument("-h", action="store_true", dest="help")
+    p.add_argument("files", nargs="*")
+    try:
+        a = p.parse_args(list(argv))
+        if a.help:
+            print(cmd_dist.__doc__, file=sys.stderr)
+            raise ValueError("")
+        if not a.files:
+            raise ValueError("no REF.msh")
+        if len(a.files) < 2:
+            raise ValueError("no QUERY")
+    except ValueError as e:
+        if str(e):
+            print(f"dist: {e}", file=sys.stderr)
+        print(DIST_USAGE, file=sys.stderr)
+        return None
+    a.ref, a.queries = a.files[0], a.files[1:]
+    return a
+
+
+def cmd_dist(argv: Sequence[str]) -> int:
+    """mash dist [-d D] [-v P] [-t] [-i] [-l] REF.msh QUERY...: the distance of every QUERY
+    sketch to every sketch of REF.msh, computed on the GPU; one row per pair on stdout
+    (reference, query, distance, p-value, shared/compared hashes), query-major.
+      -d  keep pairs with distance <= D (1)     -v  keep pairs with p-value <= P (1)
+      -t  table output (ignores -d and -v)      -l  QUERYs list paths
+      -i  one query per sequence of a FASTA QUERY
+    A QUERY ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU with
+    REF.msh's k-mer size, seed, sketch size and case rule."""
+    a = dist_args(argv)
+    if a is None:
+        return 2
+    from . import mashdist as md
+    from . import sketch as sk
+    from ._lib import Gpu
+    from .msh import load_db
+    ref = load_db(a.ref)
+    queries = expand_lists(a.queries) if a.lists else list(a.queries)
+    if not queries:
+        print("dist: no QUERY", file=sys.stderr)
+        print(DIST_USAGE, file=sys.stderr)
+        return 2
+    gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
+    dbs, fasta = [], []
+
+    def flush():      # consecutive FASTA queries are sketched in one call
+        if fasta:
+            dbs.append(sk.sketch_files(gpu, fasta, k=ref.k, seed=ref.seed, s=ref.sketch_size, individual=a.individual,
+                                       preserve_case=ref.preserve_case))
+            fasta.clear()
+
+    try:
+        md.check_compatible(ref, ref)      # a noncanonical REF.msh is refused before anything is sketched
+        for q in queries:
+            if q.endswith(".msh"):
+                flush()
+                dbs.append(load_db(q))
+                md.check_compatible(ref, dbs[-1])
+            else:
+                fasta.append(q)
+        flush()
+    except ValueError as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        return 1
+    qry = md.concat_dbs(dbs)
+    if a.table:
+        parts = list(md.dist_blocks(gpu, ref, qry, 1.0))
+        common = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, np.int32)
+        denom = np.concatenate([p[3] for p in parts]) if parts else np.zeros(0, np.int32)
+        sys.stdout.write("".join(l + "\n" for l in md.format_table(ref, qry, common, denom)))
+        return 0
+    for qi, ri, common, denom in md.dist_blocks(gpu, ref, qry, a.max_dist, block_bytes=1 << 26):
+        sys.stdout.write("".join(l + "\n" for l in md.format_lines(ref, qry, qi, ri, common, denom, a.max_dist, a.max_p)))
+    return 0
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv:
@@ -411,6 +507,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return eval_main(rest)
     if cmd == "sketch":
         return cmd_sketch(rest)
+    if cmd == "dist":
+        return cmd_dist(rest)
     print(f"unknown subcommand {cmd!r}", file=sys.stderr)
     return 2
 

@@ -1,0 +1,358 @@
+// Mash `dist` on MI355X: the (common, denom) pair of every reference sketch x query sketch of
+// two sketch DBs (the interface replaced is `mash dist REF.msh QUERY.msh`), and
+// the threshold filter over the dense result (`mash dist -d`).
+//
+// A pair.  A (reference) and B (query) are strictly ascending lists of distinct uint64 hashes,
+// truncated to their first s entries.  With U_s = the s smallest values of A u B:
+//   denom = min(s, |A u B|),   common = |A n B n U_s|
+// (Mash's merge loop, restated in DESIGN.md §Dist).  One wave computes one pair over the merged
+// sequence of the two lists (ties: A's entry first), position by position: a match is counted at
+// A's entry, and the union rank of position p is p minus the matches before p.  A pass covers a
+// range of merged positions [d0, d1): lane l takes ceil((d1 - d0) / 64) consecutive positions,
+// finds where they start in both lists by a binary search along its diagonal (the merge path)
+// and steps through them, so every lane does the same number of steps.  The first pass covers
+// [0, s).  M matches in it mean the s-th union element lies at position s + M or later, so the
+// next pass covers [s, s + M), and so on until a pass finds no match: then common = the matches
+// so far and the range end is the position of union rank s.  Unrelated lists take one pass over
+// s of their 2s entries; a range that reaches the end of both lists means |A u B| <= s.
+// The lists carry their lengths: no sentinel value, 2^64 - 1 is a hash like any other.  All
+// comparisons are unsigned 64-bit; no float arithmetic, no atomics.
+//
+// Kernels
+//   dist_tiled : a 256-thread workgroup stages a tile of TQ query sketches in LDS once, then
+//                streams its share of the references through one more LDS row; each of the 4
+//                waves takes the tile's queries w, w + 4, ... against the staged reference.
+//                HBM traffic per pair: 8 * s / TQ bytes of reference hashes + 4 bytes of result.
+//   dist_global: one wave per pair, both lists read from global memory (an s whose tile does
+//                not fit the LDS, or HYMET_DIST_PATH=global).
+//   select_count / select_write: per row of the dense block, the references whose common
+//                reaches min_common[denom], in reference order: count, hymet_scan_u32's scan,
+//                write (ballot ranks inside a row: the order is the reference order).
+#include "mm_common.hpp"
+
+#include <algorithm>
+#include <cstdlib>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxS = 16384;            // hymet_sketch_max_size(): common and denom fit 16 bits
+constexpr int kLdsBytes = 160 * 1024;   // per CU
+constexpr int kLdsHdr = 256;            // the tile's list lengths
+constexpr int kDefaultTq = 4;
+constexpr int kPre = 4;                 // reference entries per thread fetched one reference ahead
+constexpr int kMaxTq = 32;              // kLdsHdr / 4 would hold 64
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// (common << 16 | denom) of one pair; every lane of the wave calls it and gets the result.
+// PA / PB: pointer types, so that a list in LDS is read with LDS instructions.
+template <typename PA, typename PB>
+__device__ __forceinline__ uint32_t wave_pair(PA A, int la, PB B, int lb, int s) {
+    if (la == 0 || lb == 0) return (uint32_t)min(s, la + lb);  // wave-uniform; below both lists have an entry
+    const int lane = threadIdx.x & 63;
+    const int tot = la + lb;
+    int d0 = 0, d1 = min(s, tot), matches = 0;
+    for (;;) {  // merged positions [d0, d1); every bound is wave-uniform
+        const int step = (d1 - d0 + 63) >> 6;
+        const int d = min(d0 + lane * step, d1), n = min(step, d1 - d);
+        // the merge path at diagonal d: i entries of A and d - i of B come first
+        int lo = max(0, d - lb), hi = min(d, la);
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (A[mid] <= B[d - mid - 1])
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        // n steps from there.  No branch inside a step: both lists' next entries are loaded every
+        // time, at indices clamped into the lists.
+        int i = lo, j = d - lo, m = 0;
+        for (int t = 0; t < n; t++) {
+            const uint64_t a = A[min(i, la - 1)], b = B[min(j, lb - 1)];
+            const bool in_b = j < lb;
+            const bool take_a = i < la && (!in_b || a <= b);
+            m += take_a && in_b && a == b ? 1 : 0;
+            i += take_a ? 1 : 0;
+            j += take_a ? 0 : 1;
+        }
+        matches += wave_sum(m);
+        const int next = min(s + matches, tot);
+        if (next == d1) break;
+        d0 = d1;
+        d1 = next;
+    }
+    return (uint32_t)matches << 16 | (uint32_t)min(s, tot - matches);
+}
+
+// grid: n_tiles * n_chunks blocks; block b = (tile b / n_chunks, reference chunk b % n_chunks)
+__global__ __launch_bounds__(kThreads) void dist_tiled_kernel(const uint64_t *__restrict__ rh,
+                                                              const int64_t *__restrict__ roff, int64_t n_ref,
+                                                              const uint64_t *__restrict__ qh,
+                                                              const int64_t *__restrict__ qoff, int64_t q_begin,
+                                                              int64_t q_end, int s, int tq, int64_t n_chunks,
+                                                              int64_t chunk, uint32_t *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int *qlen = reinterpret_cast<int *>(smem);
+    uint64_t *Q = reinterpret_cast<uint64_t *>(smem + kLdsHdr);  // tq rows of s
+    uint64_t *R = Q + (size_t)tq * s;                            // the staged reference
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile = blockIdx.x / n_chunks, ch = blockIdx.x % n_chunks;
+    const int64_t q0 = q_begin + tile * tq;
+    const int nq = (int)min((int64_t)tq, q_end - q0);
+    const int64_t r0 = ch * chunk, r1 = min(r0 + chunk, n_ref);
+    for (int t = 0; t < nq; t++) {
+        const int64_t b = qoff[q0 + t];
+        const int len = (int)min((int64_t)s, qoff[q0 + t + 1] - b);
+        for (int e = threadIdx.x; e < len; e += kThreads) Q[(size_t)t * s + e] = qh[b + e];
+        if (threadIdx.x == 0) qlen[t] = len;
+    }
+    // The reference after the one being compared is already on its way: its first kPre * 256
+    // entries (all of them for s <= 1,024) are loaded into registers before the waves start on
+    // the staged one, and stored to LDS after the next barrier.
+    uint64_t pf[kPre];
+    int64_t nb = 0;
+    int nla = 0;
+    auto prefetch = [&](int64_t r) {
+        nb = roff[r];
+        nla = (int)min((int64_t)s, roff[r + 1] - nb);
+#pragma unroll
+        for (int u = 0; u < kPre; u++) {
+            const int e = u * kThreads + (int)threadIdx.x;
+            pf[u] = e < nla ? rh[nb + e] : 0;
+        }
+    };
+    if (r0 < r1) prefetch(r0);
+    for (int64_t r = r0; r < r1; r++) {
+        const int64_t b = nb;
+        const int la = nla;
+        __syncthreads();  // the readers of the previous reference are done
+#pragma unroll
+        for (int u = 0; u < kPre; u++) {
+            const int e = u * kThreads + (int)threadIdx.x;
+            if (e < la) R[e] = pf[u];
+        }
+        for (int e = kPre * kThreads + (int)threadIdx.x; e < la; e += kThreads) R[e] = rh[b + e];
+        __syncthreads();  // the reference (and, the first time, the query tile) is staged
+        if (r + 1 < r1) prefetch(r + 1);
+        for (int t = wave; t < nq; t += kWaves) {
+            const uint32_t v = wave_pair(R, la, Q + (size_t)t * s, qlen[t], s);
+            if (lane == 0) out[(size_t)(q0 - q_begin + t) * (size_t)n_ref + (size_t)r] = v;
+        }
+    }
+}
+
+// one wave per pair; pair p = (row p / n_ref, reference p % n_ref)
+__global__ __launch_bounds__(kThreads) void dist_global_kernel(const uint64_t *__restrict__ rh,
+                                                               const int64_t *__restrict__ roff, int64_t n_ref,
+                                                               const uint64_t *__restrict__ qh,
+                                                               const int64_t *__restrict__ qoff, int64_t q_begin,
+                                                               int64_t n_pairs, int s, uint32_t *__restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (p >= n_pairs) return;  // wave-uniform
+    const int64_t q = q_begin + p / n_ref, r = p % n_ref;
+    const int64_t rb = roff[r], qb = qoff[q];
+    const int la = (int)min((int64_t)s, roff[r + 1] - rb), lb = (int)min((int64_t)s, qoff[q + 1] - qb);
+    const uint32_t v = wave_pair(rh + rb, la, qh + qb, lb, s);
+    if ((threadIdx.x & 63) == 0) out[p] = v;
+}
+
+__device__ __forceinline__ bool select_pass(uint32_t v, const uint16_t *__restrict__ minc, int s) {
+    const uint32_t denom = v & 0xffffu;
+    return denom <= (uint32_t)s && (v >> 16) >= (uint32_t)minc[denom];
+}
+
+// one workgroup per row of the dense block
+__global__ __launch_bounds__(kThreads) void select_count_kernel(const uint32_t *__restrict__ blk, int64_t n_ref,
+                                                                const uint16_t *__restrict__ minc, int s,
+                                                                uint32_t *__restrict__ cnt) {
+    __shared__ int ws[kWaves];
+    const uint32_t *row = blk + (size_t)blockIdx.x * (size_t)n_ref;
+    int c = 0;
+    for (int64_t r = threadIdx.x; r < n_ref; r += kThreads) c += select_pass(row[r], minc, s) ? 1 : 0;
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < kWaves; w++) t += ws[w];
+        cnt[blockIdx.x] = (uint32_t)t;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void select_write_kernel(const uint32_t *__restrict__ blk, int64_t n_ref,
+                                                                const uint16_t *__restrict__ minc, int s,
+                                                                const int64_t *__restrict__ row_off, int64_t cap,
+                                                                int32_t *__restrict__ out_ref,
+                                                                uint32_t *__restrict__ out_val) {
+    __shared__ int ws[kWaves];
+    const uint32_t *row = blk + (size_t)blockIdx.x * (size_t)n_ref;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t base = row_off[blockIdx.x];
+    for (int64_t r0 = 0; r0 < n_ref; r0 += kThreads) {  // workgroup-uniform trip count
+        const int64_t r = r0 + threadIdx.x;
+        const uint32_t v = r < n_ref ? row[r] : 0u;
+        const bool keep = r < n_ref && select_pass(v, minc, s);
+        const uint64_t mask = __ballot(keep);
+        if (lane == 0) ws[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) {
+            before += w < wave ? ws[w] : 0;
+            all += ws[w];
+        }
+        const int64_t pos = base + before + __popcll(mask & ((1ull << lane) - 1));
+        if (keep && pos < cap) {
+            out_ref[pos] = (int32_t)r;
+            out_val[pos] = v;
+        }
+        base += all;
+        __syncthreads();
+    }
+}
+
+// path 0: tiled where the tile fits, 1: always the plain kernel; tq 0: the default tile
+struct DistCfg {
+    int path = 0, tq = 0;
+};
+DistCfg &cfg() {
+    static DistCfg c = [] {  // the environment is read once
+        DistCfg d;
+        const char *p = getenv("HYMET_DIST_PATH");
+        if (p && std::string(p) == "global") d.path = 1;
+        const char *t = getenv("HYMET_DIST_TQ");
+        if (t) d.tq = std::max(0, std::min(kMaxTq, atoi(t)));
+        return d;
+    }();
+    return c;
+}
+
+// query sketches per tile for sketch size s; 0: the plain path
+int tile_for(int s) {
+    const DistCfg &c = cfg();
+    if (c.path == 1 || s < 1 || s > kMaxS) return 0;
+    const int fit = (kLdsBytes - kLdsHdr) / (8 * s) - 1;  // rows beside the reference's
+    const int tq = std::min(c.tq > 0 ? c.tq : kDefaultTq, fit);
+    return tq >= 2 ? tq : 0;
+}
+
+// offsets [0, n] of a device CSR: non-decreasing, inside [0, n_hashes]
+int check_offsets(hymet_ctx *ctx, const int64_t *d_off, int64_t n, int64_t n_hashes, const char *what) {
+    std::vector<int64_t> off((size_t)n + 1);
+    HY_HIP(hipMemcpyAsync(off.data(), d_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HY_HIP(hipStreamSynchronize(ctx->stream));
+    HY_ARG(off[0] >= 0, std::string("hymet_mash_dist: ") + what + " offsets start below 0");
+    for (int64_t i = 0; i < n; i++)
+        HY_ARG(off[i] <= off[i + 1],
+               std::string("hymet_mash_dist: ") + what + " offset " + std::to_string(i + 1) + " decreases");
+    HY_ARG(off[n] <= n_hashes, std::string("hymet_mash_dist: ") + what + " offsets run past the hash array");
+    return HYMET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hymet_mash_dist_tile(int32_t s) { return tile_for(s); }
+
+int hymet_mash_dist_tune(int path, int tq) {
+    HY_ARG(path >= -1 && path <= 1 && tq >= -1 && tq <= kMaxTq, "hymet_mash_dist_tune: path in -1..1, tq in -1.." +
+                                                                     std::to_string(kMaxTq));
+    if (path >= 0) cfg().path = path;
+    if (tq >= 0) cfg().tq = tq;
+    return HYMET_OK;
+}
+
+int hymet_mash_dist(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t n_ref_hashes, const int64_t *d_ref_off,
+                    int64_t n_ref, const uint64_t *d_qry_hashes, int64_t n_qry_hashes, const int64_t *d_qry_off,
+                    int64_t n_qry, int64_t q_begin, int64_t q_end, int32_t s, uint32_t *d_out) {
+    HY_ARG(ctx, "hymet_mash_dist: null context");
+    HY_ARG(s >= 1 && s <= kMaxS, "hymet_mash_dist: sketch size must be in 1.." + std::to_string(kMaxS));
+    HY_ARG(n_ref >= 0 && n_qry >= 0 && n_ref_hashes >= 0 && n_qry_hashes >= 0, "hymet_mash_dist: negative count");
+    HY_ARG(q_begin >= 0 && q_begin <= q_end && q_end <= n_qry, "hymet_mash_dist: row range outside [0, n_qry]");
+    HY_ARG(d_ref_off && d_qry_off, "hymet_mash_dist: null offsets");
+    HY_ARG((n_ref_hashes == 0 || d_ref_hashes) && (n_qry_hashes == 0 || d_qry_hashes), "hymet_mash_dist: null hashes");
+    HY_HIP(hipSetDevice(ctx->device));
+    int rc = check_offsets(ctx, d_ref_off, n_ref, n_ref_hashes, "reference");
+    if (rc) return rc;
+    rc = check_offsets(ctx, d_qry_off, n_qry, n_qry_hashes, "query");
+    if (rc) return rc;
+    const int64_t rows = q_end - q_begin;
+    if (rows == 0 || n_ref == 0) return HYMET_OK;
+    HY_ARG(d_out, "hymet_mash_dist: null output");
+    HY_ARG(rows <= (1ll << 62) / n_ref, "hymet_mash_dist: too many pairs");
+    const int64_t n_pairs = rows * n_ref;
+    hipStream_t st = ctx->stream;
+    const int tq = tile_for(s);
+    if (tq == 0) {
+        const int64_t nb = hymet::cdiv(n_pairs, kWaves);
+        HY_ARG(nb < (1ll << 31), "hymet_mash_dist: more than 2^33 pairs in one call");
+        hymet::ProfScope _ps(ctx, "mash_dist", (8.0 * n_ref_hashes + 4.0 * n_ref) * (double)rows);
+        hipLaunchKernelGGL(dist_global_kernel, dim3((unsigned)nb), dim3(kThreads), 0, st, d_ref_hashes, d_ref_off, n_ref,
+                           d_qry_hashes, d_qry_off, q_begin, n_pairs, (int)s, d_out);
+        HY_CHECK_LAUNCH("dist_global_kernel");
+        return HYMET_OK;
+    }
+    const int64_t n_tiles = hymet::cdiv(rows, tq);
+    // enough workgroups to fill the card several times over, each with at least 16 references
+    // behind one staging of its query tile
+    int64_t n_chunks = std::max<int64_t>(1, std::min(hymet::cdiv((int64_t)ctx->n_cu * 8, n_tiles), hymet::cdiv(n_ref, 16)));
+    const int64_t chunk = hymet::cdiv(n_ref, n_chunks);
+    n_chunks = hymet::cdiv(n_ref, chunk);
+    HY_ARG(n_tiles < (1ll << 31) / n_chunks, "hymet_mash_dist: too many tiles in one call");
+    const size_t lds = (size_t)kLdsHdr + 8 * (size_t)s * (size_t)(tq + 1);
+    if (lds > 64 * 1024)
+        HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_tiled_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hymet::ProfScope _ps(ctx, "mash_dist", 8.0 * n_ref_hashes * (double)n_tiles + 4.0 * (double)n_pairs);
+    hipLaunchKernelGGL(dist_tiled_kernel, dim3((unsigned)(n_tiles * n_chunks)), dim3(kThreads), lds, st, d_ref_hashes,
+                       d_ref_off, n_ref, d_qry_hashes, d_qry_off, q_begin, q_end, (int)s, tq, n_chunks, chunk, d_out);
+    HY_CHECK_LAUNCH("dist_tiled_kernel");
+    return HYMET_OK;
+}
+
+int hymet_mash_dist_select(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n_ref,
+                           const uint16_t *d_min_common, int32_t s, int64_t *d_row_off, int32_t *d_ref_idx,
+                           uint32_t *d_val, int64_t cap, int64_t *total) {
+    HY_ARG(ctx && total, "hymet_mash_dist_select: null argument");
+    *total = 0;
+    HY_ARG(s >= 1 && s <= kMaxS, "hymet_mash_dist_select: sketch size must be in 1.." + std::to_string(kMaxS));
+    HY_ARG(n_rows >= 0 && n_rows < (1ll << 31) - 1 && n_ref >= 0 && n_ref < (1ll << 31) && cap >= 0,
+           "hymet_mash_dist_select: count out of range");
+    HY_ARG(d_row_off && d_min_common, "hymet_mash_dist_select: null argument");
+    HY_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (n_rows == 0 || n_ref == 0) {
+        HY_HIP(hipMemsetAsync(d_row_off, 0, 8 * (size_t)(n_rows + 1), st));
+        return HYMET_OK;
+    }
+    HY_ARG(d_block, "hymet_mash_dist_select: null block");
+    hymet::mm::DevBuf cnt;
+    HY_HIP(cnt.alloc(4 * (size_t)(n_rows + 1), st));
+    hymet::ProfScope _ps(ctx, "mash_dist_select", 4.0 * (double)n_rows * (double)n_ref);
+    HY_HIP(hipMemsetAsync(cnt.as<uint32_t>() + n_rows, 0, 4, st));  // the scan's last output is the total
+    hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)n_rows), dim3(kThreads), 0, st, d_block, n_ref, d_min_common,
+                       (int)s, cnt.as<uint32_t>());
+    HY_CHECK_LAUNCH("select_count_kernel");
+    int64_t t = 0;
+    const int rc = hymet::mm::exclusive_scan_u32_i64(ctx, cnt.as<uint32_t>(), d_row_off, n_rows + 1, &t);  // synchronises
+    if (rc) return rc;
+    *total = t;
+    if (t > cap)
+        return hymet::fail(HYMET_E_CAPACITY, "hymet_mash_dist_select: " + std::to_string(t) + " entries, capacity " +
+                                                 std::to_string(cap));
+    if (t == 0) return HYMET_OK;
+    HY_ARG(d_ref_idx && d_val, "hymet_mash_dist_select: null output");
+    hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)n_rows), dim3(kThreads), 0, st, d_block, n_ref, d_min_common,
+                       (int)s, d_row_off, cap, d_ref_idx, d_val);
+    HY_CHECK_LAUNCH("select_write_kernel");
+    return HYMET_OK;
+}
+
+}  // extern "C"

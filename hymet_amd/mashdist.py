@@ -1,0 +1,253 @@
+"""Dist stage: the MI355X replacement for `mash dist`, all-pairs distances between two sketch
+databases (finding redundant strains before a DB is written, placing new genomes against a
+DB, checking two DB builds against each other).
+
+Device work (libhymet_gpu.so, csrc/mash_dist.hip): `hymet_mash_dist` computes the two exact
+integers of every (reference, query) pair -- common and denom of Mash's merge loop over the
+s smallest values of the two lists' union -- and `hymet_mash_dist_select` keeps the pairs that
+pass a distance threshold.  Host work here: the distance and p-value arithmetic in double
+(the one `distance()` below both formats the output and builds the device filter's table, so
+the filter agrees exactly with the printed numbers), blocking, and the text.
+
+The semantics restate Mash's `dist` command from memory of its behaviour.  No Mash binary is
+available to check them against: they are PARITY-UNPINNED, like the .msh schema (msh.py) and
+the sketch metadata (sketch.py).  DESIGN.md §Dist holds the restated merge loop.
+"""
+from __future__ import annotations
+
+import ctypes
+import sys
+from typing import Iterator, List, Sequence, Tuple
+
+import numpy as np
+
+from .msh import SketchDB
+from .screen import binomial_upper_tail
+
+E_CAPACITY = -3
+
+
+def distance(common, denom, k: int):
+    """Mash distance of pairs with `common` shared hashes out of `denom`: 0 when common == denom
+    (0/0 included), 1 when common == 0, else -log(2j / (1 + j)) / k with j = common / denom.
+    Arrays in, float64 array out; scalars in, float out -- through the same arithmetic."""
+    c = np.asarray(common, np.float64)
+    d = np.asarray(denom, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        j = c / d
+        dist = -np.log(2.0 * j / (1.0 + j)) / float(k)
+    dist = np.where(c == 0, 1.0, dist)
+    dist = np.where(c == d, 0.0, dist)
+    return float(dist) if dist.ndim == 0 else dist
+
+
+def p_value(common: int, denom: int, len_ref: int, len_qry: int, k: int, alphabet_size: int = 4) -> float:
+    """Mash's p-value of seeing at least `common` of `denom` hashes shared by chance between
+    genomes of len_ref and len_qry bases.  A recorded length of 0 gives 1 (this project's
+    choice: Mash has no rule for it)."""
+    common, denom = int(common), int(denom)
+    if common == 0 or len_ref <= 0 or len_qry <= 0:
+        return 1.0
+    kmer_space = float(alphabet_size) ** int(k)
+    px = 1.0 / (1.0 + kmer_space / float(len_ref))
+    py = 1.0 / (1.0 + kmer_space / float(len_qry))
+    r = px * py / (px + py - px * py)
+    return binomial_upper_tail(common - 1, r, denom)
+
+
+def min_common_table(s: int, k: int, max_dist: float) -> np.ndarray:
+    """t[denom], denom in 0..s: the smallest common with distance(common, denom, k) <= max_dist,
+    or denom + 1 when there is none (uint16: the device filter keeps common >= t[denom]).
+    For max_dist < 1 the pairs that pass are exactly those with common >= t[denom]: common = 0
+    has distance 1 and from 1 up the distance falls as common grows.  (For max_dist >= 1 every
+    pair of a k >= 2 DB passes and dist_blocks does not filter on the device at all.)"""
+    s = int(s)
+    if not 1 <= s <= 0xFFFE:
+        raise ValueError(f"min_common_table: sketch size {s} outside 1..65534")
+    d = np.arange(s + 1, dtype=np.int64)
+    if max_dist >= 1.0:
+        first = np.where(distance(np.zeros(s + 1), d, k) <= max_dist, 0, d + 1)
+        # common = 0 aside, the walk below still finds the smallest passing common
+    else:
+        first = d + 1
+    # bisection over common in 1..denom, all denoms at once: distance(denom, denom) = 0
+    lo = np.ones(s + 1, np.int64)
+    hi = d.copy()
+    ok = (d >= 1) & (distance(d, d, k) <= max_dist)          # false everywhere for max_dist < 0
+    while True:
+        act = ok & (lo < hi)
+        if not act.any():
+            break
+        mid = (lo + hi) // 2
+        passes = distance(mid, d, k) <= max_dist
+        hi = np.where(act & passes, mid, hi)
+        lo = np.where(act & ~passes, mid + 1, lo)
+    t = np.where(ok, np.minimum(first, hi), first)
+    if max_dist >= 0.0:
+        t[0] = 0                                              # 0/0: distance 0
+    return t.astype(np.uint16)
+
+
+def _warn(msg: str):
+    print(f"WARNING: {msg}", file=sys.stderr)
+
+
+def check_compatible(ref_db: SketchDB, qry_db: SketchDB, warn: bool = True) -> int:
+    """The sketch size to compare two DBs at (the smaller of the two; one warning on stderr when
+    they differ).  ValueError when k, seed, alphabet or strand rule differ, and for
+    noncanonical DBs, which this project does not build (`cli sketch` refuses -n)."""
+    if qry_db.k != ref_db.k:
+        raise ValueError(f"The query sketch has a kmer size ({qry_db.k}) that does not match the reference ({ref_db.k}).")
+    if qry_db.seed != ref_db.seed:
+        raise ValueError(f"The query sketch has a hash seed ({qry_db.seed}) that does not match the reference "
+                         f"({ref_db.seed}).")
+    if qry_db.alphabet != ref_db.alphabet:
+        raise ValueError(f"The query sketch has an alphabet ({qry_db.alphabet}) that does not match the reference "
+                         f"({ref_db.alphabet}).")
+    if bool(qry_db.noncanonical) != bool(ref_db.noncanonical):
+        raise ValueError("The query sketch and the reference differ in strand handling (noncanonical).")
+    if ref_db.noncanonical:
+        raise ValueError("Noncanonical sketches are not supported.")
+    s = min(int(ref_db.sketch_size), int(qry_db.sketch_size))
+    if s < 1:
+        raise ValueError("A sketch database records a sketch size of 0.")
+    if warn and ref_db.sketch_size != qry_db.sketch_size:
+        _warn(f"The query sketch size ({qry_db.sketch_size}) does not match the reference ({ref_db.sketch_size}); "
+              f"comparing at the smaller ({s}).")
+    return s
+
+
+def concat_dbs(dbs: Sequence[SketchDB]) -> SketchDB:
+    """Several sketch DBs (already checked against one reference) as one, entries in argument
+    order; its sketch size is the smallest of theirs."""
+    first = dbs[0]
+    if len(dbs) == 1:
+        return first
+    off = np.zeros(sum(d.n_refs for d in dbs) + 1, np.int64)
+    pos = at = 0
+    for d in dbs:
+        off[at + 1:at + d.n_refs + 1] = np.asarray(d.offsets[1:d.n_refs + 1], np.int64) - int(d.offsets[0]) + pos
+        at += d.n_refs
+        pos += int(d.offsets[d.n_refs]) - int(d.offsets[0])
+    return SketchDB(k=first.k, seed=first.seed, sketch_size=min(int(d.sketch_size) for d in dbs), alphabet=first.alphabet,
+                    preserve_case=first.preserve_case, noncanonical=first.noncanonical,
+                    names=[n for d in dbs for n in d.names], comments=[c for d in dbs for c in d.comments],
+                    lengths=np.concatenate([np.asarray(d.lengths, np.int64)[:d.n_refs] for d in dbs]), offsets=off,
+                    hashes=np.concatenate([np.asarray(d.hashes, np.uint64)[int(d.offsets[0]):int(d.offsets[d.n_refs])]
+                                           for d in dbs]))
+
+
+class DeviceSketches:
+    """A sketch DB's CSR in HBM."""
+
+    def __init__(self, gpu, db: SketchDB):
+        torch = gpu.torch
+        self.n = int(db.n_refs)
+        off = np.ascontiguousarray(np.asarray(db.offsets, np.int64)[:self.n + 1])
+        h = np.ascontiguousarray(np.asarray(db.hashes, np.uint64))
+        self.n_hashes = len(h)
+        self.hashes = torch.from_numpy(h.view(np.int64).copy()).to(gpu.dev) if len(h) else gpu.zeros(1, torch.int64)
+        self.offsets = torch.from_numpy(off.copy()).to(gpu.dev)
+
+
+def dist_block(gpu, ref: DeviceSketches, qry: DeviceSketches, q_begin: int, q_end: int, s: int):
+    """The dense (q_end - q_begin) x ref.n device tensor (int32 bits of common << 16 | denom)."""
+    from ._lib import ptr
+    torch = gpu.torch
+    out = gpu.empty(max(1, (q_end - q_begin) * ref.n), torch.int32)
+    gpu.call("hymet_mash_dist", ptr(ref.hashes), ref.n_hashes, ptr(ref.offsets), ref.n, ptr(qry.hashes), qry.n_hashes,
+             ptr(qry.offsets), qry.n, int(q_begin), int(q_end), int(s), ptr(out))
+    return out
+
+
+def select_block(gpu, block, n_rows: int, n_ref: int, table, s: int, cap: int = 0):
+    """hymet_mash_dist_select over a dense device block: (row_off int64 [n_rows + 1], ref index
+    int32, packed value uint32) on the host.  Retries once with the reported total when the
+    first capacity was too small."""
+    from ._lib import check, ptr
+    torch = gpu.torch
+    row_off = gpu.empty(n_rows + 1, torch.int64)
+    cap = int(cap) if cap > 0 else max(1024, (n_rows * n_ref) // 16)
+    total = ctypes.c_int64()
+    while True:
+        idx = gpu.empty(cap, torch.int32)
+        val = gpu.empty(cap, torch.int32)
+        rc = gpu.lib.hymet_mash_dist_select(gpu.ctx, ptr(block), n_rows, n_ref, ptr(table), int(s), ptr(row_off), ptr(idx),
+                                            ptr(val), cap, ctypes.byref(total))
+        if rc == E_CAPACITY and total.value > cap:
+            cap = total.value
+            continue
+        check(rc, "hymet_mash_dist_select")
+        break
+    gpu.sync()
+    n = total.value
+    return row_off.cpu().numpy(), idx[:n].cpu().numpy(), val[:n].cpu().numpy().view(np.uint32)
+
+
+def dist_blocks(gpu, ref_db: SketchDB, qry_db: SketchDB, max_dist: float = 1.0,
+                block_bytes: int = 1 << 30) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+    """`mash dist` of two DBs on the device: yields (q_index, r_index, common, denom) int32
+    arrays, query-major (for each query in DB order, the references in DB order), one tuple per
+    block of queries.  Both DBs are uploaded once; a block holds as many queries as keep the
+    dense result within block_bytes, and the concatenated result does not depend on it.
+    max_dist >= 1: every pair; below, the pairs with distance() <= max_dist, filtered on the
+    device (min_common_table)."""
+    s = check_compatible(ref_db, qry_db, warn=False)
+    torch = gpu.torch
+    ref, qry = DeviceSketches(gpu, ref_db), DeviceSketches(gpu, qry_db)
+    n_ref = ref.n
+    rows = max(1, int(block_bytes) // (4 * max(n_ref, 1)))
+    table = None
+    if max_dist < 1.0:
+        table = torch.from_numpy(min_common_table(s, ref_db.k, max_dist).view(np.int16).copy()).to(gpu.dev)
+    for q0 in range(0, qry.n, rows):
+        q1 = min(qry.n, q0 + rows)
+        nq = q1 - q0
+        block = dist_block(gpu, ref, qry, q0, q1, s)
+        if n_ref == 0:
+            z = np.zeros(0, np.int32)
+            yield z, z, z, z
+            continue
+        if table is None:
+            gpu.sync()
+            v = block[:nq * n_ref].cpu().numpy().view(np.uint32)
+            qi = np.repeat(np.arange(q0, q1, dtype=np.int32), n_ref)
+            ri = np.tile(np.arange(n_ref, dtype=np.int32), nq)
+        else:
+            row_off, ri, v = select_block(gpu, block, nq, n_ref, table, s)
+            qi = np.repeat(np.arange(q0, q1, dtype=np.int32), np.diff(row_off))
+        yield qi, ri, (v >> 16).astype(np.int32), (v & 0xFFFF).astype(np.int32)
+
+
+def format_lines(ref_db: SketchDB, qry_db: SketchDB, q_index, r_index, common, denom, max_dist: float = 1.0,
+                 max_p: float = 1.0) -> List[str]:
+    """`mash dist` rows: reference name, query name, distance, p-value, common/denom, tab
+    separated, floats as %g (C++ ostream default, as format_screen); pairs with a distance above
+    max_dist or a p-value above max_p are dropped."""
+    k, asz = ref_db.k, len(ref_db.alphabet) or 4
+    dist = np.atleast_1d(distance(common, denom, k))
+    out = []
+    memo = {}
+    for n in range(len(dist)):
+        if not dist[n] <= max_dist:
+            continue
+        q, r, c, d = int(q_index[n]), int(r_index[n]), int(common[n]), int(denom[n])
+        key = (c, d, int(ref_db.lengths[r]), int(qry_db.lengths[q]))
+        p = memo.get(key)
+        if p is None:
+            p = memo[key] = p_value(c, d, key[2], key[3], k, asz)
+        if p > max_p:
+            continue
+        out.append("%s\t%s\t%g\t%g\t%d/%d" % (ref_db.names[r], qry_db.names[q], dist[n], p, c, d))
+    return out
+
+
+def format_table(ref_db: SketchDB, qry_db: SketchDB, common, denom) -> List[str]:
+    """`mash dist -t`: a header `#query`, the reference names; then one row per query: its name
+    and the distance to every reference (%g).  common / denom: n_qry x n_ref, query-major."""
+    n_q, n_r = qry_db.n_refs, ref_db.n_refs
+    dist = np.atleast_1d(distance(common, denom, ref_db.k)).reshape(n_q, n_r)
+    out = ["\t".join(["#query"] + [str(n) for n in ref_db.names])]
+    for q in range(n_q):
+        out.append("\t".join([str(qry_db.names[q])] + ["%g" % x for x in dist[q]]))
+    return out

@@ -225,6 +225,40 @@ int hymet_sketch_batch(hymet_ctx *ctx, const uint32_t *d_2b, const uint32_t *d_m
                        const int64_t *h_chunk_begin, const int64_t *h_chunk_end, int32_t n_sketches,
                        uint64_t *d_out, int32_t *d_out_n);
 
+/* ------------------------------------------------------------ Mash dist (sketch vs sketch)
+ * Replaces `mash dist REF.msh QUERY.msh`: for every (reference, query) pair of two sketch DBs
+ * the shared-hash count over the s smallest values of the two lists' union.  A list is a
+ * strictly ascending run of distinct uint64 hashes (32-bit sketches widened); only its first s
+ * entries are read.  denom = min(s, |A u B|), common = |A n B n (the s smallest of A u B)|;
+ * distance and p-value are host arithmetic on the two integers (hymet_amd/mashdist.py).
+ * Both DBs are device CSR: hashes (n_*_hashes uint64) and n + 1 int64 offsets.  Rows are the
+ * queries [q_begin, q_end); d_out is the dense (q_end - q_begin) x n_ref array, row-major, of
+ * common << 16 | denom.  s in 1..hymet_sketch_max_size().  Checked before anything is launched
+ * (the offsets are copied to the host for it, which synchronises the context's stream): offsets
+ * non-decreasing and inside the hash arrays, the row range inside [0, n_qry], s in range; a
+ * violation returns HYMET_E_ARG.  The kernel is queued on the context's stream; zero rows or
+ * zero references is not an error. */
+int hymet_mash_dist(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t n_ref_hashes, const int64_t *d_ref_off,
+                    int64_t n_ref, const uint64_t *d_qry_hashes, int64_t n_qry_hashes, const int64_t *d_qry_off,
+                    int64_t n_qry, int64_t q_begin, int64_t q_end, int32_t s, uint32_t *d_out);
+/* The query sketches a workgroup of hymet_mash_dist keeps in LDS for sketch size s; 0 when s
+ * takes the plain kernel (one wave per pair, both lists from global memory): the tile does not
+ * fit the LDS, or HYMET_DIST_PATH=global is set (read once, at the first call). */
+int hymet_mash_dist_tile(int32_t s);
+/* Overrides what the environment gave, for A/B timing inside one process: path 0 = tiled where
+ * it fits, 1 = the plain kernel for every s; tq = query sketches per tile (0 = the default; the
+ * HYMET_DIST_TQ variable sets the same).  -1 leaves a setting as it is.  Process-wide. */
+int hymet_mash_dist_tune(int path, int tq);
+/* `mash dist -d`: per row of a dense block (n_rows x n_ref, as hymet_mash_dist writes it) the
+ * references with common >= d_min_common[denom] (s + 1 uint16 entries, built by the host from
+ * the distance threshold), in reference order, as a CSR: d_row_off (n_rows + 1 int64), then
+ * reference index and packed value per entry.  Count per row, hymet_scan_u32's scan, write: the
+ * order is deterministic.  *total = the number of entries (always set); when it exceeds cap the
+ * call returns HYMET_E_CAPACITY with d_row_off written and no entry written.  Synchronises. */
+int hymet_mash_dist_select(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n_ref,
+                           const uint16_t *d_min_common, int32_t s, int64_t *d_row_off, int32_t *d_ref_idx,
+                           uint32_t *d_val, int64_t cap, int64_t *total);
+
 /* --------------------------------------------------- minimizer index (minimap2 -d)
  * Replaces `minimap2 -I2g -d reference.mmi combined_genomes.fasta` (scripts/minimap2.sh:12):
  * default indexing parameters k=15, w=10 (no -x at build time), one handle per -I part.
