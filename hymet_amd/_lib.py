@@ -52,6 +52,7 @@ _SIGS = {
     "hymet_screen_count": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _u32, _i32, _c.POINTER(_vp), _c.POINTER(_i64),
                                   _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_vp), _u64, _vp, _i64, _vp, _vp]),
     "hymet_screen_stats": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hymet_screen_winner": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "hymet_sketch_max_size": (_i64, []),
     "hymet_sketch_batch": (_i32, [_vp, _vp, _vp, _i64, _i32, _u32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
     "hymet_mash_dist": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),

@@ -2,6 +2,7 @@
 
     python -m hymet_amd.cli screen  INPUT_DIR DB.msh SCREEN_TAB FILTERED SORTED TOP_HITS SELECTED THRESH
         == scripts/mash.sh:4-55 (mash screen -p 8 -v 0.9, sort -u -k5,5, sort -gr, threshold walk)
+           HYMET_SCREEN_WINNER=1 in the environment: mash screen -w (winner-take-all) instead
     python -m hymet_amd.cli limit --selected F --output F [--score-file F]... [--max N] [--dedupe] ...
         == scripts/limit_candidates.py:47-89,249-289
     python -m hymet_amd.cli map     INPUT_DIR REFERENCE_FASTA INDEX_PATH PAF_OUT
@@ -28,6 +29,8 @@
     python -m hymet_amd.cli dist [-d D] [-v P] [-t] [-i] [-l] REF.msh QUERY...
         == mash dist (all-pairs distances between sketch DBs; QUERY is .msh or FASTA; like
            sketch, not a stage of the reference workflow)
+    python -m hymet_amd.cli mash-screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE...
+        == mash screen (the rows on stdout, in sketch order; -w: winner-take-all)
 
 The thin wrappers under scripts/ call these, so run_hymet_cami.sh / main.pl can use them
 in place of the reference stage scripts unchanged.  All device work goes through
@@ -57,11 +60,28 @@ def _write_lines(path: str, lines: Sequence[str]):
 
 
 # ------------------------------------------------------------------ screen (mash.sh)
+def screen_winner_env(environ=None) -> bool:
+    """HYMET_SCREEN_WINNER: 1 / true / yes / on switch the screen stage to `mash screen -w`;
+    unset, empty, 0 / false / no / off leave it as the reference runs it.  Anything else is an
+    error (a typo must not silently change the candidate list)."""
+    v = (os.environ if environ is None else environ).get("HYMET_SCREEN_WINNER", "").strip().lower()
+    if v in ("", "0", "false", "no", "off"):
+        return False
+    if v in ("1", "true", "yes", "on"):
+        return True
+    raise ValueError(f"HYMET_SCREEN_WINNER={v!r}: expected 1 or 0")
+
+
 def cmd_screen(argv: Sequence[str]) -> int:
     if len(argv) != 8:
         print("usage: screen INPUT_DIR DB.msh SCREEN_TAB FILTERED SORTED TOP_HITS SELECTED THRESH", file=sys.stderr)
         return 2
     input_dir, msh_path, screen_tab, filtered, sorted_p, top_hits, selected, thresh = argv
+    try:
+        winner = screen_winner_env()
+    except ValueError as e:
+        print(f"screen: {e}", file=sys.stderr)
+        return 2
     from . import screen as scr
     from . import select as sel
     from ._lib import Gpu
@@ -73,7 +93,7 @@ def cmd_screen(argv: Sequence[str]) -> int:
     rows: List[str] = []
     if files:
         ss = read_fasta(files)
-        res = scr.screen(gpu, DevicePool(gpu, ss, DevicePool.ALPHA_MASH), [db])[0]
+        res = scr.screen(gpu, DevicePool(gpu, ss, DevicePool.ALPHA_MASH), [db], winner=winner)[0]
         rows = res.lines(v_max=0.9)
     _write_lines(screen_tab, rows)
     f_rows = sel.sort_unique_k5(rows)
@@ -474,6 +494,65 @@ def cmd_dist(argv: Sequence[str]) -> int:
     return 0
 
 
+# ------------------------------------------------------------------ mash-screen (mash screen)
+MASH_SCREEN_USAGE = "usage: mash-screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE..."
+
+
+def mash_screen_args(argv: Sequence[str]):
+    """`mash screen`'s flag letters.  Returns the parsed namespace, or None after printing the
+    usage line (unknown flag, no DB.msh, no FILE)."""
+    class _Parser(argparse.ArgumentParser):
+        def error(self, message):
+            raise ValueError(message)
+
+    p = _Parser(prog="mash-screen", add_help=False, allow_abbrev=False)
+    p.add_argument("-w", action="store_true", dest="winner")
+    p.add_argument("-i", type=float, default=0.0, dest="min_identity")
+    p.add_argument("-v", type=float, default=1.0, dest="max_p")
+    p.add_argument("-h", action="store_true", dest="help")
+    p.add_argument("files", nargs="*")
+    try:
+        a = p.parse_args(list(argv))
+        if a.help:
+            print(cmd_mash_screen.__doc__, file=sys.stderr)
+            raise ValueError("")
+        if not a.files:
+            raise ValueError("no DB.msh")
+        if len(a.files) < 2:
+            raise ValueError("no input FILE")
+    except ValueError as e:
+        if str(e):
+            print(f"mash-screen: {e}", file=sys.stderr)
+        print(MASH_SCREEN_USAGE, file=sys.stderr)
+        return None
+    a.db, a.inputs = a.files[0], a.files[1:]
+    return a
+
+
+def cmd_mash_screen(argv: Sequence[str]) -> int:
+    """mash screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE...: how well each sketch of
+    DB.msh is contained in the pooled FILEs (FASTA, gzip too), computed on the GPU; one row per
+    reference on stdout in sketch order (identity, shared-hashes, median-multiplicity, p-value,
+    name, comment).
+      -w  winner-take-all: each hash found in the pool is credited to the best-scoring
+          reference holding it, and the rows are recomputed from the credited hashes
+      -i  keep rows with identity >= MIN_IDENTITY (0; negative: also references sharing nothing)
+      -v  keep rows with p-value <= MAX_P (1)"""
+    a = mash_screen_args(argv)
+    if a is None:
+        return 2
+    from . import screen as scr
+    from ._lib import Gpu
+    from .msh import load_db
+    from .seqio import DevicePool, read_fasta
+    db = load_db(a.db)
+    gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
+    ss = read_fasta(list(a.inputs))
+    res = scr.screen(gpu, DevicePool(gpu, ss, DevicePool.ALPHA_MASH), [db], winner=a.winner)[0]
+    sys.stdout.write("".join(l + "\n" for l in res.lines(v_max=a.max_p, identity_min=a.min_identity)))
+    return 0
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv:
@@ -509,6 +588,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return cmd_sketch(rest)
     if cmd == "dist":
         return cmd_dist(rest)
+    if cmd == "mash-screen":
+        return cmd_mash_screen(rest)
     print(f"unknown subcommand {cmd!r}", file=sys.stderr)
     return 2
 

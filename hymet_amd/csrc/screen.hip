@@ -25,6 +25,11 @@
 //   screen_stats   : one 256-thread block per reference: gather its counts through the
 //                    canonical map, shared = #>0, median = k-th smallest positive count by a
 //                    bisection over the value range with block reductions (no sort).
+//   screen_claim   : winner-take-all (mash screen -w): one block per competing reference (first-
+//                    pass shared > 0, ranked on the host, best first); every hit key keeps the
+//                    best rank among its holders (atomicMin on a uint32 per canonical index).
+//                    screen_stats<winner> then counts, per competing reference, only the keys it
+//                    won.  Work is O(hashes of the competing references) + one fill of `win`.
 // Roofline: HBM/latency bound (random 8-B key probes); algorithmic bytes per k-mer are
 // 0.375 (packed read) + 8 per DB probe (+4 per hit), DESIGN.md §Screen.
 #include "common.hpp"
@@ -204,18 +209,49 @@ __device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t *red) {
 
 constexpr int kStatsLds = 4096;
 
-__global__ __launch_bounds__(256) void screen_stats_kernel(const int64_t *__restrict__ ref_off,
+// winner-take-all (mash screen -w): the competing references (first-pass shared > 0) come in
+// rank order, best first, so a reference's priority is its position in d_comp.  Every key with
+// a hit takes the smallest priority among its holders: one atomicMin per held hit key.
+__global__ __launch_bounds__(256) void screen_claim_kernel(const int64_t *__restrict__ ref_off, int64_t n_refs,
                                                            const int32_t *__restrict__ canon_of,
-                                                           const uint32_t *__restrict__ counts, uint32_t *shared,
+                                                           const uint32_t *__restrict__ counts,
+                                                           const int32_t *__restrict__ comp, uint32_t *win) {
+    const int64_t r = comp[blockIdx.x];
+    if (r < 0 || r >= n_refs) return;
+    const int64_t b = ref_off[r], n = ref_off[r + 1] - b;
+    for (int64_t j = threadIdx.x; j < n; j += blockDim.x) {
+        const int32_t c = canon_of[b + j];
+        if (counts[c] > 0) atomicMin(&win[c], (uint32_t)blockIdx.x);
+    }
+}
+
+// what DB hash j of the block's reference contributes: its key's count; with WINNER only when
+// the key was credited to this reference (win[key] == the block's priority), else 0
+template <bool WINNER>
+__device__ __forceinline__ uint32_t stat_value(const int32_t *__restrict__ canon_of, const uint32_t *__restrict__ counts,
+                                               const uint32_t *__restrict__ win, int64_t j) {
+    const int32_t c = canon_of[j];
+    if (WINNER && win[c] != (uint32_t)blockIdx.x) return 0;
+    return counts[c];
+}
+
+// one block per reference (WINNER: per competing reference comp[blockIdx.x], priority blockIdx.x)
+template <bool WINNER>
+__global__ __launch_bounds__(256) void screen_stats_kernel(const int64_t *__restrict__ ref_off, int64_t n_refs,
+                                                           const int32_t *__restrict__ canon_of,
+                                                           const uint32_t *__restrict__ counts,
+                                                           const int32_t *__restrict__ comp,
+                                                           const uint32_t *__restrict__ win, uint32_t *shared,
                                                            uint32_t *median) {
     __shared__ uint32_t vals[kStatsLds];
     __shared__ uint32_t red[8];
-    const int64_t r = blockIdx.x;
+    const int64_t r = WINNER ? (int64_t)comp[blockIdx.x] : (int64_t)blockIdx.x;
+    if (r < 0 || r >= n_refs) return;
     const int64_t b = ref_off[r], n = ref_off[r + 1] - b;
     const bool in_lds = n <= kStatsLds;
     uint32_t pos = 0, mx = 0;
     for (int64_t j = threadIdx.x; j < n; j += blockDim.x) {
-        const uint32_t c = counts[canon_of[b + j]];
+        const uint32_t c = stat_value<WINNER>(canon_of, counts, win, b + j);
         if (in_lds) vals[j] = c;
         pos += c > 0;
         mx = max(mx, c);
@@ -230,7 +266,7 @@ __global__ __launch_bounds__(256) void screen_stats_kernel(const int64_t *__rest
             const uint32_t mid = lo + (hi - lo) / 2;
             uint32_t cnt = 0;
             for (int64_t j = threadIdx.x; j < n; j += blockDim.x) {
-                const uint32_t c = in_lds ? vals[j] : counts[canon_of[b + j]];
+                const uint32_t c = in_lds ? vals[j] : stat_value<WINNER>(canon_of, counts, win, b + j);
                 cnt += (c > 0 && c <= mid);
             }
             cnt = block_sum<uint32_t>(cnt, red);
@@ -354,9 +390,29 @@ int hymet_screen_stats(hymet_ctx *ctx, const int64_t *d_ref_off, int64_t n_refs,
     HY_ARG(n_refs < (1ll << 31), "hymet_screen_stats: too many references");
     HY_HIP(hipSetDevice(ctx->device));
     hymet::ProfScope _ps(ctx, "screen_stats");  // O(H) gather, bytes not modelled
-    hipLaunchKernelGGL(screen_stats_kernel, dim3((unsigned)n_refs), dim3(256), 0, ctx->stream, d_ref_off, d_canon_of,
-                       d_counts, d_shared, d_median);
+    hipLaunchKernelGGL(screen_stats_kernel<false>, dim3((unsigned)n_refs), dim3(256), 0, ctx->stream, d_ref_off, n_refs,
+                       d_canon_of, d_counts, (const int32_t *)nullptr, (const uint32_t *)nullptr, d_shared, d_median);
     HY_CHECK_LAUNCH("screen_stats_kernel");
+    return HYMET_OK;
+}
+
+int hymet_screen_winner(hymet_ctx *ctx, const int64_t *d_ref_off, int64_t n_refs, const int32_t *d_canon_of,
+                        const uint32_t *d_counts, int64_t n_hashes, const int32_t *d_comp, int64_t n_comp,
+                        uint32_t *d_win, uint32_t *d_shared, uint32_t *d_median) {
+    HY_ARG(ctx && d_ref_off && d_canon_of && d_counts && d_win && d_shared && d_median, "hymet_screen_winner: null argument");
+    HY_ARG(n_hashes >= 0 && n_hashes < (1ll << 31) - 1, "hymet_screen_winner: n_hashes out of range");
+    HY_ARG(n_comp >= 0 && n_comp <= n_refs && n_refs < (1ll << 31), "hymet_screen_winner: n_comp must be 0..n_refs");
+    if (n_comp == 0) return HYMET_OK;
+    HY_ARG(d_comp, "hymet_screen_winner: d_comp is null");
+    HY_HIP(hipSetDevice(ctx->device));
+    hymet::ProfScope _ps(ctx, "screen_winner", (double)(n_hashes + 1) * 4.0);  // the fill; the gathers are not modelled
+    HY_HIP(hipMemsetAsync(d_win, 0xFF, (size_t)(n_hashes + 1) * 4, ctx->stream));  // unclaimed: all ones (no priority is 2^32 - 1)
+    hipLaunchKernelGGL(screen_claim_kernel, dim3((unsigned)n_comp), dim3(256), 0, ctx->stream, d_ref_off, n_refs, d_canon_of,
+                       d_counts, d_comp, d_win);
+    HY_CHECK_LAUNCH("screen_claim_kernel");
+    hipLaunchKernelGGL(screen_stats_kernel<true>, dim3((unsigned)n_comp), dim3(256), 0, ctx->stream, d_ref_off, n_refs,
+                       d_canon_of, d_counts, d_comp, (const uint32_t *)d_win, d_shared, d_median);
+    HY_CHECK_LAUNCH("screen_stats_kernel<winner>");
     return HYMET_OK;
 }
 

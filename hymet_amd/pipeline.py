@@ -51,6 +51,7 @@ class Config:
     map_streams: int = 2              # concurrent mapping batches (library contexts / HIP streams)
     n_input_files: int = 1            # run_hymet_cami.sh copies one FASTA into input/
     limit: bool = True                # run_hymet_cami.sh:101-126; main.pl has no limit step (False)
+    screen_winner: bool = False       # mash screen -w: winner-take-all screen (the reference runs without)
     # Every run re-reads its inputs, as the reference's stage processes do: `mash screen`
     # loads each sketch DB (S1, when the DBs are given as .msh paths) and
     # classification_cami.py loads detailed_taxonomy.tsv + taxonomy_hierarchy.tsv (C1-C2).
@@ -583,7 +584,7 @@ class Pipeline:
 
     def screen_select(self, pool):
         t0 = time.perf_counter()
-        res = scr.screen(self.gpu, pool, self.dbs, self.tables, self.comm)
+        res = scr.screen(self.gpu, pool, self.dbs, self.tables, self.comm, winner=self.cfg.screen_winner)
         self.last_screen = res
         ph = getattr(self, "phases", None)
         if ph is not None:                    # the screen's share of run()'s screen_select_s

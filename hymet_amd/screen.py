@@ -74,6 +74,15 @@ class ScreenResult:
     median: np.ndarray
     set_size: int
     n_kmers: int
+    winner: bool = False                        # shared / median are winner-take-all (mash screen -w)
+    shared_first: Optional[np.ndarray] = None   # the first pass (every reference on its own):
+    median_first: Optional[np.ndarray] = None   # shared / median themselves unless winner
+
+    def __post_init__(self):
+        if self.shared_first is None:
+            self.shared_first = self.shared
+        if self.median_first is None:
+            self.median_first = self.median
 
     def lines(self, v_max: float = 0.9, identity_min: float = 0.0) -> List[str]:
         return format_screen(self.db, self.shared, self.median, self.set_size, v_max, identity_min)
@@ -176,8 +185,53 @@ def table_stats(gpu, t: ScreenTable, counts):
     return sh[:n].cpu().numpy().view(np.uint32).copy(), md[:n].cpu().numpy().view(np.uint32).copy()
 
 
-def screen(gpu, pool, dbs: Sequence[SketchDB], tables: Optional[Sequence[ScreenTable]] = None, comm=None) -> List[ScreenResult]:
-    """Screen the pool against every DB.  DBs sharing (k, seed) are probed in one pass."""
+def mash_identity(shared: int, sketch_len: int, k: int) -> float:
+    """Mash's containment identity of a reference: 1 when every hash of its sketch was found,
+    else (shared / sketch_len)^(1/k) in double.  The output rows' first column, and the score
+    winner-take-all ranks the references by."""
+    if shared == sketch_len:
+        return 1.0
+    return 0.0 if shared == 0 else math.pow(shared / sketch_len, 1.0 / k)
+
+
+def rank_competitors(db: SketchDB, shared) -> np.ndarray:
+    """Winner-take-all order of the references that can hold a hit key (first-pass shared > 0):
+    identity descending, then genome length descending, then reference index ascending (Mash
+    leaves this last tie to its hash set's iteration order).  Lengths count as 0 unless the DB
+    has one per reference.  Returns the reference indices (int32), best first."""
+    comp = np.flatnonzero(np.asarray(shared)[:db.n_refs])
+    if len(comp) == 0:
+        return comp.astype(np.int32)
+    off = db.offsets
+    score = np.array([mash_identity(int(shared[i]), int(off[i + 1] - off[i]), db.k) for i in comp], np.float64)
+    lengths = np.asarray(db.lengths)
+    length = lengths[comp].astype(np.int64) if len(lengths) == db.n_refs else np.zeros(len(comp), np.int64)
+    order = np.lexsort((comp, -length, -score))     # last key first: score, then length, then index
+    return comp[order].astype(np.int32)
+
+
+def table_winner(gpu, t: ScreenTable, counts, shared):
+    """Winner-take-all shared / median of one table from its hit counts and first-pass shared."""
+    torch = gpu.torch
+    n = t.db.n_refs
+    comp = rank_competitors(t.db, shared)
+    if len(comp) == 0:          # no hit: nothing to credit, nothing launched
+        return np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    sh = gpu.zeros(n, torch.int32)
+    md = gpu.zeros(n, torch.int32)
+    win = gpu.empty(t.n_hashes + 1, torch.int32)
+    d_comp = torch.from_numpy(comp).to(gpu.dev)
+    gpu.call("hymet_screen_winner", ptr(t.ref_off), n, ptr(t.canon_of), ptr(counts), t.n_hashes, ptr(d_comp), len(comp),
+             ptr(win), ptr(sh), ptr(md))
+    return sh.cpu().numpy().view(np.uint32).copy(), md.cpu().numpy().view(np.uint32).copy()
+
+
+def screen(gpu, pool, dbs: Sequence[SketchDB], tables: Optional[Sequence[ScreenTable]] = None, comm=None,
+           winner: bool = False) -> List[ScreenResult]:
+    """Screen the pool against every DB.  DBs sharing (k, seed) are probed in one pass.
+    winner: `mash screen -w`, each DB on its own: every hit key is credited to the best-scoring
+    reference holding it and shared / median are recounted from the credited keys (the first
+    pass stays in shared_first / median_first)."""
     tables = list(tables) if tables is not None else [ScreenTable(gpu, db) for db in dbs]
     results: List[Optional[ScreenResult]] = [None] * len(dbs)
     groups = {}
@@ -201,7 +255,11 @@ def screen(gpu, pool, dbs: Sequence[SketchDB], tables: Optional[Sequence[ScreenT
             for ci, i in enumerate(chunk):
                 sh, md = table_stats(gpu, tables[i], counts[ci])
                 b_i = bottom[:dbs[i].sketch_size]
-                results[i] = ScreenResult(dbs[i], sh, md, set_size_from_bottom(b_i, k), nk)
+                if winner:
+                    sh_w, md_w = table_winner(gpu, tables[i], counts[ci], sh)
+                    results[i] = ScreenResult(dbs[i], sh_w, md_w, set_size_from_bottom(b_i, k), nk, True, sh, md)
+                else:
+                    results[i] = ScreenResult(dbs[i], sh, md, set_size_from_bottom(b_i, k), nk)
     return results
 
 
@@ -261,7 +319,7 @@ def format_screen(db: SketchDB, shared, median, set_size, v_max=0.9, identity_mi
         if x == 0 and identity_min >= 0.0:
             continue
         sl = int(off[i + 1] - off[i])
-        ident = 1.0 if x == sl else (0.0 if x == 0 else math.pow(x / sl, 1.0 / k))
+        ident = mash_identity(x, sl, k)
         if ident < identity_min:
             continue
         pv = 1.0 if x == 0 else binomial_upper_tail(x - 1, r, sl)

@@ -203,6 +203,17 @@ int hymet_screen_count(hymet_ctx *ctx, const uint32_t *d_2b, const uint32_t *d_m
 int hymet_screen_stats(hymet_ctx *ctx, const int64_t *d_ref_off, int64_t n_refs,
                        const int32_t *d_canon_of, const uint32_t *d_counts, uint32_t *d_shared,
                        uint32_t *d_median);
+/* Winner-take-all statistics (`mash screen -w`): every key with a hit is credited to one of the
+ * references holding it.  d_comp lists the n_comp competing references (those with first-pass
+ * shared > 0, each at most once) in rank order, best first; a key goes to the holder that comes
+ * first in d_comp.  For each listed reference r, d_shared[r] = #keys credited to it and
+ * d_median[r] = their sorted counts[shared/2] (0 when none); entries of other references are
+ * not written (caller-zeroed).  d_win: n_hashes + 1 uint32 of scratch (the winner's rank per
+ * canonical index), reset here.  n_comp == 0 launches nothing. */
+int hymet_screen_winner(hymet_ctx *ctx, const int64_t *d_ref_off, int64_t n_refs,
+                        const int32_t *d_canon_of, const uint32_t *d_counts, int64_t n_hashes,
+                        const int32_t *d_comp, int64_t n_comp, uint32_t *d_win, uint32_t *d_shared,
+                        uint32_t *d_median);
 
 /* ------------------------------------------------------------ Mash sketch (DB build)
  * Replaces `mash sketch` for building the sketch DBs the screen reads (the reference workflow
