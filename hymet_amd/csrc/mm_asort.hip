@@ -8,19 +8,28 @@
 // over ~47 key bits (six 8-bit passes over 12 B per anchor) is replaced by work local to a
 // query:
 //   * a query of <= 4096 anchors is sorted whole in one block;
-//   * a larger query is cut into tiles of 4096 anchors; every tile counts its anchors per
+//   * a larger query is cut into tiles of 16384 anchors; every tile counts its anchors per
 //     bin = (rev, rid) in LDS; a per-query scan turns the counts into each (tile, bin) run's
 //     position and lists the non-empty bins -- the (query, strand, target) groups; the tiles
-//     scatter their anchors to their runs; every group of <= 4096 anchors is then sorted by
-//     (rpos, y) in one block, and the larger groups (a query against its own genome) by one
-//     device radix sort over all of them together (key = group rank | key bits below the bin).
-// A block sort packs (the key's bits below q or below rid, y) into one 64-bit word, sorts it
-// in registers (bitonic, ITEMS per thread) and merges the runs in LDS: merge path splits,
-// then each thread's outputs by a bitonic half-cleaner over two windows of ITEMS words
-// (independent LDS loads instead of a serial merge).  Segments of <= 64 anchors take a wave
-// bitonic sort on (key, y), those of <= 8 a register network in one thread; class lists
-// are filled with one global atomic per class and block.  Equal keys after the device radix
-// sort (one target position hit by several query minimizers) are put in y order on write.
+//     scatter their anchors to their runs, a bin's anchors staying in input order; every group
+//     of <= 16384 anchors is then sorted by (rpos, y) in one block, and the larger groups (a
+//     query against its own genome) by one device radix sort over all of them together (key =
+//     group rank | key bits below the bin).
+// A block sort packs (the key's bits below q or below rid, y) into one 64-bit word.  The keys
+// are emitted minimizer by minimizer in query order, each minimizer's hits in index order, so
+// inside a group they already rise in rpos (+ strand) or fall (- strand) but for stray hits
+// elsewhere in the target (about 1 % of the anchors): the block first looks for that shape --
+// a sorted backbone and at most 128 outliers, found by flagging both ends of every descent for
+// up to three passes -- sorts the outliers in one wave and writes every word to its final
+// place (block_seg_sort_kernel; HYMET_ASORT_ADAPT=0 turns this off).  Any other segment (a
+// whole query, a shuffled group) is sorted in registers (bitonic, ITEMS per thread) and its
+// runs merged in LDS: merge path splits, then each thread's outputs by a bitonic half-cleaner
+// over two windows of ITEMS words (independent LDS loads instead of a serial merge).  The
+// result is the same either way: the words are distinct up to identical (rpos, y) pairs.
+// Segments of <= 64 anchors take a wave bitonic sort on (key, y), those of <= 8 a register
+// network in one thread; class lists are filled with one global atomic per class and block.
+// Equal keys after the device radix sort (one target position hit by several query
+// minimizers) are put in y order on write.
 // Index parts of more than 2047 targets use coarse bins of 2^cs consecutive targets (the
 // bin histogram always fits LDS), sorted inside by (low target bits, rpos, y).  The caller
 // falls back to the device sort of the whole batch (return 1) when the packed words would
@@ -281,14 +290,51 @@ __global__ __launch_bounds__(1024) void query_scan_kernel(const Seg *large, cons
 // round of kSub anchors is ranked by bin in LDS (wave-aggregated atomics), its bin counts are
 // scanned, the round is laid out bin by bin in LDS, and written run by run (consecutive lanes,
 // consecutive addresses).
-// LDS per block: 12 B per round anchor + 8 B per bin (sized to the part's bins at launch:
-// 1024 bins and 2048 anchors = 32 KB, five blocks per CU; measured on C4: 3072 anchors in a
-// static 68 KB was 323 ms/step of mm_anchor_gsort, 44 KB dynamic 300, 2048 anchors 288)
+//
+// A bin's anchors leave a round in input order (ORDERED): write_anchor_keys_kernel emits a
+// group's anchors rising (+ strand) or falling (- strand) in rpos but for stray hits, and the
+// block sorts' outlier path lives on that order.  Every wave ranks a contiguous quarter of the
+// round into counters of its own -- its rows one after the other, a row's lanes of one bin in
+// lane order (wave_rank_ordered) -- and a wave's ranks start after the earlier waves' counts.
+// The counters are 16-bit (a round holds kSub < 65536 anchors) and wave-private, so they take
+// plain loads and stores.  Unordered (the ranks of lds_rank, in the order the LDS serialises
+// the waves' atomics) only where the ordered counters would pass 64 KB of LDS: 4096 bins.
+// LDS per block: 12 B per round anchor + 4 B per bin + the rank counters, 8 B per bin ordered
+// (four waves x 16 bits), 4 B unordered; sized to the part's bins at launch: 1024 bins and 2048
+// anchors = 36 KB, four blocks per CU (measured on C4: 3072 anchors in a static 68 KB was
+// 323 ms/step of mm_anchor_gsort, 44 KB dynamic 300, 2048 anchors in 32 KB 288)
 #ifndef HYMET_SCATTER_SUB
 #define HYMET_SCATTER_SUB 2048
 #endif
 constexpr int kSub = HYMET_SCATTER_SUB;
+static_assert(kSub % 256 == 0 && kSub < 65536, "scatter round: whole rows of 256, 16-bit ranks");
 
+constexpr size_t scatter_lds(int nbins, bool ordered) { return (size_t)kSub * 12 + (size_t)nbins * (ordered ? 12 : 8); }
+// ordered ranking where its LDS fits the 64 KB a launch gets without opting in for more
+constexpr bool scatter_ordered(int nbins) { return scatter_lds(nbins, true) <= 65536; }
+
+// The rank of every active lane among the earlier anchors of its bin in the wave's part of the
+// round, h[bin] counted up: the lanes of a row that share a bin find each other with one ballot
+// per bin bit, rank in lane order, and their lowest lane updates the wave's counter.
+__device__ __forceinline__ uint32_t wave_rank_ordered(uint16_t *h, int bin, bool active, int bin_bits) {
+    const int lane = threadIdx.x & 63;
+    uint64_t peers = __ballot(active);
+    for (int i = 0; i < bin_bits; i++) {
+        const bool bit = bin >> i & 1;
+        const uint64_t m = __ballot(bit);
+        peers &= bit ? m : ~m;
+    }
+    const int leader = active ? __ffsll((unsigned long long)peers) - 1 : lane;
+    uint32_t base = 0;
+    if (active && lane == leader) {
+        base = h[bin];
+        h[bin] = (uint16_t)(base + (uint32_t)__popcll(peers));
+    }
+    base = (uint32_t)__shfl((int)base, leader, 64);
+    return base + (uint32_t)__popcll(peers & ((1ull << lane) - 1));
+}
+
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__restrict__ key, const uint32_t *__restrict__ val,
                                                            const int64_t *__restrict__ tile_a0, const int32_t *__restrict__ tile_q,
                                                            const int32_t *__restrict__ tile_n, const int64_t *__restrict__ qoff,
@@ -298,7 +344,9 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__res
     uint64_t *sk = smem;                                   // [kSub]
     uint32_t *sv = reinterpret_cast<uint32_t *>(sk + kSub);  // [kSub]
     uint32_t *c = sv + kSub;                               // [nbins] run position of every bin for the next round
-    uint32_t *lo = c + nbins;                              // [nbins] round: bin counts, then their exclusive offsets
+    // the round's bin counts, then their exclusive offsets; ordered: per wave, cw[w * nbins + b]
+    uint32_t *lo = c + nbins;                              // [nbins] (unordered)
+    uint16_t *cw = reinterpret_cast<uint16_t *>(lo);       // [4][nbins] (ordered)
     __shared__ uint32_t wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t a0 = tile_a0[blockIdx.x];
@@ -307,29 +355,40 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__res
     for (int b = tid; b < nbins; b += 256) c[b] = row[b];
     const int64_t base = qoff[tile_q[blockIdx.x]];
     const int per = (nbins + 255) / 256, b0 = min(tid * per, nbins), b1 = min(b0 + per, nbins);
+    const int bin_bits = 31 - __clz(nbins);
+    // a thread's anchors of a round: ordered, row j of its wave's quarter; else row j of the round
+    constexpr int kRows = kSub / 256;
+    const int e_first = ORDERED ? w * (kSub / 4) + lane : tid, e_step = ORDERED ? 64 : 256;
     for (int r0 = 0; r0 < n; r0 += kSub) {
         const int m = min(kSub, n - r0);
-        for (int b = tid; b < nbins; b += 256) lo[b] = 0;
+        if (ORDERED) {
+            for (int b = tid; b < 2 * nbins; b += 256) lo[b] = 0;  // cw, as words
+        } else {
+            for (int b = tid; b < nbins; b += 256) lo[b] = 0;
+        }
         __syncthreads();
-        uint64_t kk[kSub / 256];
-        uint32_t vv[kSub / 256], rk[kSub / 256];
-        int bn[kSub / 256];
+        uint64_t kk[kRows];
+        uint32_t vv[kRows], rk[kRows];
+        int bn[kRows];
 #pragma unroll
-        for (int j = 0; j < kSub / 256; j++) {  // the round's loads first, at clamped positions
-            const int e = min(j * 256 + tid, m - 1);
+        for (int j = 0; j < kRows; j++) {  // the round's loads first, at clamped positions
+            const int e = min(e_first + j * e_step, m - 1);
             kk[j] = key[a0 + r0 + e];
             vv[j] = val[a0 + r0 + e];
         }
 #pragma unroll
-        for (int j = 0; j < kSub / 256; j++) {  // every lane runs the loop (wave-level ballots inside)
-            const bool act = j * 256 + tid < m;
+        for (int j = 0; j < kRows; j++) {  // every lane runs the loop (wave-level ballots inside)
+            const bool act = e_first + j * e_step < m;
             bn[j] = (int)((kk[j] >> pb) & (uint64_t)(nbins - 1));
-            rk[j] = lds_rank(lo, bn[j], act);
+            rk[j] = ORDERED ? wave_rank_ordered(cw + w * nbins, act ? bn[j] : 0, act, bin_bits) : lds_rank(lo, bn[j], act);
         }
         __syncthreads();
         {  // exclusive scan of the bin counts: per-thread spans, then a block scan of span sums
             uint32_t sum = 0;
-            for (int b = b0; b < b1; b++) sum += lo[b];
+            for (int b = b0; b < b1; b++) {
+                if (ORDERED) sum += (uint32_t)cw[b] + cw[nbins + b] + cw[2 * nbins + b] + cw[3 * nbins + b];
+                else sum += lo[b];
+            }
             uint32_t inc = sum;
             for (int d = 1; d < 64; d <<= 1) {
                 const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64);
@@ -340,29 +399,43 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__res
             uint32_t ex = inc - sum;
             for (int k = 0; k < w; k++) ex += wsum[k];
             for (int b = b0; b < b1; b++) {
-                const uint32_t t = lo[b];
-                lo[b] = ex;
-                ex += t;
+                if (ORDERED) {  // wave k's anchors of the bin after those of the waves before it
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t t = cw[k * nbins + b];
+                        cw[k * nbins + b] = (uint16_t)ex;
+                        ex += t;
+                    }
+                } else {
+                    const uint32_t t = lo[b];
+                    lo[b] = ex;
+                    ex += t;
+                }
             }
         }
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < kSub / 256; j++)
-            if (j * 256 + tid < m) {
-                const uint32_t slot = lo[bn[j]] + rk[j];
+        for (int j = 0; j < kRows; j++)
+            if (e_first + j * e_step < m) {
+                const uint32_t slot = (ORDERED ? (uint32_t)cw[w * nbins + bn[j]] : lo[bn[j]]) + rk[j];
                 sk[slot] = kk[j];
                 sv[slot] = vv[j];
             }
         __syncthreads();
+        // the bin's first slot of the round: the first wave's offset where ordered
         for (int s = tid; s < m; s += 256) {
             const uint64_t k = sk[s];
             const int b = (int)((k >> pb) & (uint64_t)(nbins - 1));
-            const int64_t pos = base + c[b] + (s - lo[b]);
+            const int64_t pos = base + c[b] + (s - (ORDERED ? (uint32_t)cw[b] : lo[b]));
             okey[pos] = k;
             oval[pos] = sv[s];
         }
         __syncthreads();
-        for (int b = tid; b < nbins; b += 256) c[b] += (b + 1 < nbins ? lo[b + 1] : (uint32_t)m) - lo[b];
+        for (int b = tid; b < nbins; b += 256) {
+            const uint32_t cur = ORDERED ? (uint32_t)cw[b] : lo[b];
+            const uint32_t nxt = b + 1 < nbins ? (ORDERED ? (uint32_t)cw[b + 1] : lo[b + 1]) : (uint32_t)m;
+            c[b] += nxt - cur;
+        }
         __syncthreads();
     }
 }
@@ -485,17 +558,58 @@ __device__ __forceinline__ void reg_sort(uint64_t (&k)[N]) {
             }
 }
 
+// most outliers the outlier path of a block sort takes: one wave sorts them, one or two words
+// per lane (A/B knob, 64 or 128; measured: 64 finishes 96.3 % of the block-sorted anchors of
+// C4 and 69.9 % of the Zymo-backbone workload's, 128 98.5 % and 84.7 %)
+#ifndef HYMET_ASORT_OUTMAX
+#define HYMET_ASORT_OUTMAX 128
+#endif
+constexpr int kOutMax = HYMET_ASORT_OUTMAX;
+static_assert(kOutMax == 64 || kOutMax == 128, "the outlier sort holds one or two words per lane");
+// what the block sorts did, counted where the caller asks (hymet_mm_anchor_sort): segments and
+// anchors finished by the outlier path, segments and anchors that took the full sort
+enum { kStFastSegs = 0, kStFastAnchors, kStFullSegs, kStFullAnchors, kStats };
+
+// first position in the ascending o[lo, hi) whose word is not below x
+__device__ __forceinline__ int lower_bound64(const uint64_t *o, int lo, int hi, uint64_t x) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (o[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // one block of BLOCK threads per segment of <= BLOCK * ITEMS anchors: packed words
-// w = (key bits [0, nbits)) << ybits | y sorted by register networks + LDS merge path
+// w = (key bits [0, nbits)) << ybits | y sorted by register networks + LDS merge path.
+//
+// Before that, the outlier path (adapt): a (query, strand, target) group arrives as a rising
+// -- on the - strand falling -- backbone plus a few stray hits, so the segment, read back to
+// front where its first word is above its last, is split into a sorted rest and <= kOutMax
+// outliers: both ends of every descent are flagged, then both ends of every descent among the
+// words still unflagged, for at most three such passes; a pass that flags nothing proves the
+// rest sorted.  One wave sorts the outliers, and every word goes straight to its final place:
+// a kept word to its rank among the kept words plus the outliers below it, an outlier to its
+// rank among the outliers plus the kept words not above it (kept before outlier on a tie).
+// The cost does not depend on the class's padded capacity.  A segment that is not of that
+// shape (a whole query, a shuffled group) takes the full sort from the words already staged.
 template <int BLOCK, int ITEMS>
 __global__ __launch_bounds__(BLOCK) void block_seg_sort_kernel(const Seg *list, const uint64_t *key, const uint32_t *val,
-                                                               int nbits, int ybits, AnchorOut out) {
+                                                               int nbits, int ybits, AnchorOut out, int adapt,
+                                                               unsigned long long *stats) {
     constexpr int CAP = BLOCK * ITEMS;
+    static_assert(ITEMS <= 16 && BLOCK % 64 == 0, "flag words hold 16 bits per thread; whole waves");
     __shared__ uint64_t sm[CAP + CAP / 16];
+    // outlier path: per thread, the flags of its words (low half) and those other threads set
+    // in the running pass (high half); words flagged per pass; outliers; wave sums
+    __shared__ uint32_t fmw[BLOCK], pcnt[4], wsum[BLOCK / 64];
+    __shared__ uint64_t ol[kOutMax];
     const Seg S = list[blockIdx.x];
     const int tid = threadIdx.x;
     const uint64_t lm = (1ull << nbits) - 1, ym = (1ull << ybits) - 1;
     const uint64_t hi_bits = key[S.s] & ~lm;
+    fmw[tid] = 0;
+    if (tid < 4) pcnt[tid] = 0;
     {  // coalesced load, striped: every row's loads issued before any is used (clamped positions)
         uint64_t kr[ITEMS];
         uint32_t vr[ITEMS];
@@ -513,46 +627,184 @@ __global__ __launch_bounds__(BLOCK) void block_seg_sort_kernel(const Seg *list, 
     }
     __syncthreads();
     uint64_t k[ITEMS];
+    bool done = false;  // block-uniform: the outlier path has every word at its place in sm
+    if (adapt) {
+        const int n = S.n;
+        const bool rev = sm[0] > sm[lds_ix(n - 1)];
+        // word e of the segment in the order the path reads it; past its end, the padding
+        auto at = [&](int e) -> uint64_t { return e < n ? sm[lds_ix(rev ? n - 1 - e : e)] : ~0ull; };
 #pragma unroll
-    for (int j = 0; j < ITEMS; j++) k[j] = sm[lds_ix(tid * ITEMS + j)];
-    reg_sort<ITEMS>(k);
-    for (int run = ITEMS; run < CAP; run <<= 1) {
+        for (int j = 0; j < ITEMS; j++) k[j] = at(tid * ITEMS + j);
+        constexpr uint32_t kFull = (1u << ITEMS) - 1;
+        uint32_t fl = 0;        // the thread's flagged words
+        int total = 0;          // the block's
+        uint64_t prev = 0;      // the last unflagged word before the thread's own
+        bool has_prev = false;
+        // passes 0..2 flag, a pass that finds nothing to flag ends the search; pass 3 only checks
+        for (int p = 0; p < 4; p++) {
+            int pt = -1, pj = 0;
+            for (int t = tid - 1; t >= 0; t--) {  // bounded: <= kOutMax words are flagged
+                const uint32_t m = fmw[t] & kFull;
+                if (m != kFull) {
+                    pt = t;
+                    pj = 31 - __clz((int)(~m & kFull));
+                    break;
+                }
+            }
+            has_prev = pt >= 0;
+            prev = has_prev ? at(pt * ITEMS + pj) : 0;
+            uint32_t nf = 0;
+            uint64_t cur = prev;
+            int ct = pt, cj = pj;
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++)
+                if (!(fl >> j & 1)) {
+                    if (ct >= 0 && k[j] < cur) {  // a descent: both ends
+                        nf |= 1u << j;
+                        if (ct == tid) nf |= 1u << cj;
+                        else atomicOr(&fmw[ct], 0x10000u << cj);
+                    }
+                    cur = k[j];
+                    ct = tid;
+                    cj = j;
+                }
+            __syncthreads();
+            nf |= fmw[tid] >> 16;
+            fl |= nf;
+            fmw[tid] = fl;
+            if (nf) atomicAdd(&pcnt[p], (uint32_t)__popc(nf));
+            __syncthreads();
+            const int cn = (int)pcnt[p];
+            if (cn == 0) {
+                done = true;
+                break;
+            }
+            total += cn;
+            if (total > kOutMax) break;
+        }
+        if (done && total > 0) {
+            const int lane = tid & 63, w = tid >> 6;
+            const uint32_t c = (uint32_t)__popc(fl);
+            uint32_t inc = c;  // flagged words before the thread's own: waves, then the wave sums
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64);
+                if (lane >= d) inc += o;
+            }
+            if (lane == 63) wsum[w] = inc;
+            __syncthreads();
+            uint32_t fb = inc - c;
+            for (int i = 0; i < w; i++) fb += wsum[i];
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++)
+                if (fl >> j & 1) ol[fb + (uint32_t)__popc(fl & ((1u << j) - 1))] = k[j];
+            __syncthreads();
+            if (tid < 64 && total <= 64) {  // the first wave sorts the outliers (bitonic, a word per lane)
+                uint64_t v = tid < total ? ol[tid] : ~0ull;
+                for (int ww = 2; ww <= 64; ww <<= 1)
+                    for (int j = ww >> 1; j > 0; j >>= 1) {
+                        const uint64_t ov = shfl_xor64(v, j);
+                        const bool up = (tid & ww) == 0, lower = (tid & j) == 0;
+                        if ((lower == up) == (ov < v)) v = ov;
+                    }
+                ol[tid] = v;
+            } else if (kOutMax > 64 && tid < 64) {  // two words per lane: elements tid and tid + 64
+                uint64_t v[2] = {ol[tid], tid + 64 < total ? ol[(tid + 64) % kOutMax] : ~0ull};
+                for (int ww = 2; ww <= 128; ww <<= 1)
+                    for (int j = ww >> 1; j > 0; j >>= 1) {
+                        if (j == 64) {  // the last merge's first step: within the lane, ascending
+                            const uint64_t a = min(v[0], v[1]), b = max(v[0], v[1]);
+                            v[0] = a;
+                            v[1] = b;
+                            continue;
+                        }
+#pragma unroll
+                        for (int r = 0; r < 2; r++) {
+                            const uint64_t ov = shfl_xor64(v[r], j);
+                            const bool up = ((tid + 64 * r) & ww) == 0, lower = (tid & j) == 0;
+                            if ((lower == up) == (ov < v[r])) v[r] = ov;
+                        }
+                    }
+                ol[tid] = v[0];
+                ol[(tid + 64) % kOutMax] = v[1];
+            }
+            __syncthreads();
+            // Every word to its place.  lcur: outliers below the last kept word handled so far; a
+            // kept word of rank r (among the kept) with lj outliers below it goes to r + lj, and
+            // the outliers [lcur, lj) -- not below its predecessor, below it -- to their index + r.
+            int lcur = has_prev ? lower_bound64(ol, 0, total, prev) : 0;
+            const uint32_t kept = ~fl & kFull;
+            if (kept) {
+                uint64_t last = 0;
+#pragma unroll
+                for (int j = 0; j < ITEMS; j++)
+                    if (kept >> j & 1) last = k[j];
+                const int lend = lower_bound64(ol, lcur, total, last);
+                int r = tid * ITEMS - (int)fb;
+#pragma unroll
+                for (int j = 0; j < ITEMS; j++)
+                    if (kept >> j & 1) {
+                        const int lj = lcur == lend ? lcur : lower_bound64(ol, lcur, lend, k[j]);
+                        for (int i = lcur; i < lj; i++) sm[lds_ix(i + r)] = ol[i];
+                        sm[lds_ix(r + lj)] = k[j];
+                        lcur = lj;
+                        r++;
+                    }
+            }
+            // outliers above every kept word (a full segment: no padding above them)
+            if (tid == BLOCK - 1)
+                for (int i = lcur; i < total; i++) sm[lds_ix(i + CAP - total)] = ol[i];
+        } else if (done && rev) {
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) sm[lds_ix(tid * ITEMS + j)] = k[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < ITEMS; j++) k[j] = sm[lds_ix(tid * ITEMS + j)];
+    }
+    if (stats && tid == 0) {
+        atomicAdd(stats + (done ? kStFastSegs : kStFullSegs), 1ull);
+        atomicAdd(stats + (done ? kStFastAnchors : kStFullAnchors), (unsigned long long)S.n);
+    }
+    if (!done) {  // the full sort: register networks, then merge rounds
+        reg_sort<ITEMS>(k);
+        for (int run = ITEMS; run < CAP; run <<= 1) {
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) sm[lds_ix(tid * ITEMS + j)] = k[j];
+            __syncthreads();
+            const int o = tid * ITEMS, base = o & ~(2 * run - 1), diag = o - base;
+            const int a0 = base, b0 = base + run;
+            int lo = max(0, diag - run), hi = min(diag, run);
+            while (lo < hi) {  // merge path: first lo with A[lo] > B[diag - 1 - lo]
+                const int mid = (lo + hi) >> 1;
+                if (sm[lds_ix(a0 + mid)] <= sm[lds_ix(b0 + diag - 1 - mid)]) lo = mid + 1;
+                else hi = mid;
+            }
+            // the thread's ITEMS outputs are the ITEMS smallest of A[ai..] and B[bi..]: min(A[ai + j],
+            // B[bi + ITEMS-1-j]) holds exactly those as a bitonic sequence -- independent LDS
+            // loads and a half-cleaner network instead of a serial merge
+            const int ai = a0 + lo, bi = b0 + diag - lo;
+            const int ae = a0 + run, be = b0 + run;
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) {
+                const int ia = ai + j, ib = bi + ITEMS - 1 - j;
+                const uint64_t va = ia < ae ? sm[lds_ix(ia)] : ~0ull, vb = ib < be ? sm[lds_ix(ib)] : ~0ull;
+                k[j] = min(va, vb);
+            }
+#pragma unroll
+            for (int d = ITEMS >> 1; d > 0; d >>= 1)
+#pragma unroll
+                for (int i = 0; i < ITEMS; i++)
+                    if ((i & d) == 0) {
+                        const uint64_t x = k[i], y = k[i + d];
+                        k[i] = min(x, y);
+                        k[i + d] = max(x, y);
+                    }
+        }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < ITEMS; j++) sm[lds_ix(tid * ITEMS + j)] = k[j];
-        __syncthreads();
-        const int o = tid * ITEMS, base = o & ~(2 * run - 1), diag = o - base;
-        const int a0 = base, b0 = base + run;
-        int lo = max(0, diag - run), hi = min(diag, run);
-        while (lo < hi) {  // merge path: first lo with A[lo] > B[diag - 1 - lo]
-            const int mid = (lo + hi) >> 1;
-            if (sm[lds_ix(a0 + mid)] <= sm[lds_ix(b0 + diag - 1 - mid)]) lo = mid + 1;
-            else hi = mid;
-        }
-        // the thread's ITEMS outputs are the ITEMS smallest of A[ai..] and B[bi..]: min(A[ai + j],
-        // B[bi + ITEMS-1-j]) holds exactly those as a bitonic sequence -- independent LDS
-        // loads and a half-cleaner network instead of a serial merge
-        const int ai = a0 + lo, bi = b0 + diag - lo;
-        const int ae = a0 + run, be = b0 + run;
-#pragma unroll
-        for (int j = 0; j < ITEMS; j++) {
-            const int ia = ai + j, ib = bi + ITEMS - 1 - j;
-            const uint64_t va = ia < ae ? sm[lds_ix(ia)] : ~0ull, vb = ib < be ? sm[lds_ix(ib)] : ~0ull;
-            k[j] = min(va, vb);
-        }
-#pragma unroll
-        for (int d = ITEMS >> 1; d > 0; d >>= 1)
-#pragma unroll
-            for (int i = 0; i < ITEMS; i++)
-                if ((i & d) == 0) {
-                    const uint64_t x = k[i], y = k[i + d];
-                    k[i] = min(x, y);
-                    k[i + d] = max(x, y);
-                }
     }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < ITEMS; j++) sm[lds_ix(tid * ITEMS + j)] = k[j];
     __syncthreads();
     for (int e = tid; e < S.n; e += BLOCK) {  // coalesced write
         const uint64_t w = sm[lds_ix(e)], wp = sm[lds_ix(e > 0 ? e - 1 : 0)];
@@ -621,11 +873,17 @@ int bits_of(int64_t v) {
 
 // sort the segments of `lists` (class-major, capacity cap; counts hc), all but the large class
 int sort_segments(hymet_ctx *ctx, const Seg *lists, int64_t cap, const int32_t *hc, const uint64_t *key,
-                  const uint32_t *val, int nbits, int ybits, const AnchorOut &out) {
+                  const uint32_t *val, int nbits, int ybits, const AnchorOut &out, unsigned long long *stats) {
     hipStream_t st = ctx->stream;
+    // HYMET_ASORT_ADAPT=0: the block sorts without their outlier path (A/B timing, tests)
+    static const int adapt = [] {
+        const char *e = getenv("HYMET_ASORT_ADAPT");
+        return e && e[0] == '0' ? 0 : 1;
+    }();
 #define HY_SEG_LAUNCH(cls, kern, block)                                                                                     \
     if (hc[cls] > 0) {                                                                                                      \
-        hipLaunchKernelGGL(kern, dim3((unsigned)hc[cls]), dim3(block), 0, st, lists + cls * cap, key, val, nbits, ybits, out); \
+        hipLaunchKernelGGL(kern, dim3((unsigned)hc[cls]), dim3(block), 0, st, lists + cls * cap, key, val, nbits, ybits, out, \
+                           adapt, stats);                                                                                   \
         HY_CHECK_LAUNCH(#kern);                                                                                             \
     }
     if (hc[kThread] > 0) {
@@ -665,7 +923,7 @@ int sort_segments(hymet_ctx *ctx, const Seg *lists, int64_t cap, const int32_t *
 
 int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val, int64_t n, const int64_t *d_qoff, int n_q,
                         int rb, int pb, uint64_t yhi, int64_t max_qlen, uint64_t *okey, uint32_t *oval, uint64_t *ax,
-                        uint64_t *ay, uint32_t *hb, uint32_t *ax32) {
+                        uint64_t *ay, uint32_t *hb, uint32_t *ax32, unsigned long long *d_stats) {
     // bins = (strand, target) -- or, for parts of more than 2047 targets, (strand, target >> cs):
     // coarse bins of 2^cs consecutive targets, sorted inside by (low target bits, rpos, y)
     const int cs = std::max(0, 1 + rb - 12);
@@ -691,7 +949,7 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
     }
     ProfScope _ps(ctx, "mm_anchor_gsort", 52.0 * (double)n);  // key+y read, scatter write, sort read, x+y write
     // 2 small queries: sorted whole
-    int rc = sort_segments(ctx, qlists.as<Seg>(), n_q, hq, key, val, 1 + rb + pb, ybits, out);
+    int rc = sort_segments(ctx, qlists.as<Seg>(), n_q, hq, key, val, 1 + rb + pb, ybits, out, d_stats);
     if (rc || hq[kLarge] == 0) return rc;
     // 3 large queries: tiles, bin histograms, per-query scan, scatter
     const int nl = hq[kLarge];
@@ -720,8 +978,12 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
                        H.as<uint32_t>(), groups.as<Seg>(), gcap, ctx->dctr + kCtrGroups, mb_dev(ctx, kMbGroups));
     HY_CHECK_LAUNCH("query_scan_kernel");
     HY_ARG(nbins >= 1 && nbins <= kMaxBins, "grouped_anchor_sort: bin count out of range");
-    hipLaunchKernelGGL(tile_scatter_kernel, dim3((unsigned)NT), dim3(256), (size_t)kSub * 12 + (size_t)nbins * 8, st, key, val, ta0.as<int64_t>(), tq.as<int32_t>(),
-                       tn.as<int32_t>(), d_qoff, gb, nbins, H.as<uint32_t>(), okey, oval);
+    if (scatter_ordered(nbins))
+        hipLaunchKernelGGL(tile_scatter_kernel<true>, dim3((unsigned)NT), dim3(256), scatter_lds(nbins, true), st, key, val,
+                           ta0.as<int64_t>(), tq.as<int32_t>(), tn.as<int32_t>(), d_qoff, gb, nbins, H.as<uint32_t>(), okey, oval);
+    else
+        hipLaunchKernelGGL(tile_scatter_kernel<false>, dim3((unsigned)NT), dim3(256), scatter_lds(nbins, false), st, key, val,
+                           ta0.as<int64_t>(), tq.as<int32_t>(), tn.as<int32_t>(), d_qoff, gb, nbins, H.as<uint32_t>(), okey, oval);
     HY_CHECK_LAUNCH("tile_scatter_kernel");
     // 4 groups of the large queries, sorted in place by (rpos, y)
     HY_HIP(hipStreamSynchronize(st));
@@ -739,7 +1001,7 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
         hg[c] = (int32_t)mb_read(ctx, kMbGClass + c);
         if (hg[c] < 0 || hg[c] > G) return hymet::fail(HYMET_E_INTERNAL, "grouped_anchor_sort: group class count > cap");
     }
-    rc = sort_segments(ctx, glists.as<Seg>(), (int64_t)G, hg, okey, oval, gb, ybits, out);
+    rc = sort_segments(ctx, glists.as<Seg>(), (int64_t)G, hg, okey, oval, gb, ybits, out, d_stats);
     if (rc) return rc;
     if (hg[kLarge] > 0) {
         const int nbig = hg[kLarge];
@@ -774,3 +1036,48 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
 
 }  // namespace mm
 }  // namespace hymet
+
+extern "C" int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const uint32_t *h_val, int64_t n,
+                                    const int64_t *h_qoff, int32_t n_q, int32_t rb, int32_t pb, uint64_t yhi,
+                                    int64_t max_qlen, uint64_t *h_ax, uint64_t *h_ay, uint32_t *h_ax32, uint32_t *h_hb,
+                                    int64_t *h_stats) {
+    using hymet::mm::DevBuf;
+    HY_ARG(ctx && h_key && h_val && h_qoff && h_ax && h_ay && h_ax32 && h_hb, "hymet_mm_anchor_sort: null argument");
+    HY_ARG(n > 0 && n < INT32_MAX && n_q > 0, "hymet_mm_anchor_sort: n or n_q out of range");
+    HY_ARG(rb >= 0 && pb >= 1 && rb + pb < 63 && max_qlen >= 0, "hymet_mm_anchor_sort: key layout out of range");
+    HY_ARG(h_qoff[0] == 0 && h_qoff[n_q] == n, "hymet_mm_anchor_sort: query offsets do not span the anchors");
+    for (int32_t q = 0; q < n_q; q++) HY_ARG(h_qoff[q] <= h_qoff[q + 1], "hymet_mm_anchor_sort: query offsets not rising");
+    HY_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf key, val, qoff, okey, oval, ax, ay, ax32, hb, stats;
+    const size_t hb_bytes = hymet::mm::head_bits_bytes(n);
+    HY_HIP(key.alloc(8 * (size_t)n, st));
+    HY_HIP(val.alloc(4 * (size_t)n, st));
+    HY_HIP(qoff.alloc(8 * (size_t)(n_q + 1), st));
+    HY_HIP(okey.alloc(8 * (size_t)n, st));
+    HY_HIP(oval.alloc(4 * (size_t)n, st));
+    HY_HIP(ax.alloc(8 * (size_t)n, st));
+    HY_HIP(ay.alloc(8 * (size_t)n, st));
+    HY_HIP(ax32.alloc(4 * (size_t)n, st));
+    HY_HIP(hb.alloc(hb_bytes, st));
+    HY_HIP(stats.alloc(8 * hymet::mm::kStats, st));
+    HY_HIP(hipMemcpyAsync(key.p, h_key, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(val.p, h_val, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(qoff.p, h_qoff, 8 * (size_t)(n_q + 1), hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemsetAsync(stats.p, 0, 8 * hymet::mm::kStats, st));
+    const int rc = hymet::mm::grouped_anchor_sort(ctx, key.as<uint64_t>(), val.as<uint32_t>(), n, qoff.as<int64_t>(), n_q, rb,
+                                                  pb, yhi, max_qlen, okey.as<uint64_t>(), oval.as<uint32_t>(),
+                                                  ax.as<uint64_t>(), ay.as<uint64_t>(), hb.as<uint32_t>(),
+                                                  ax32.as<uint32_t>(), h_stats ? stats.as<unsigned long long>() : nullptr);
+    if (rc) {
+        HY_HIP(hipStreamSynchronize(st));  // the uploads read the caller's arrays
+        return rc;
+    }
+    HY_HIP(hipMemcpyAsync(h_ax, ax.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HY_HIP(hipMemcpyAsync(h_ay, ay.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HY_HIP(hipMemcpyAsync(h_ax32, ax32.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HY_HIP(hipMemcpyAsync(h_hb, hb.p, 4 * (size_t)((n + 31) / 32), hipMemcpyDeviceToHost, st));
+    if (h_stats) HY_HIP(hipMemcpyAsync(h_stats, stats.p, 8 * hymet::mm::kStats, hipMemcpyDeviceToHost, st));
+    HY_HIP(hipStreamSynchronize(st));
+    return HYMET_OK;
+}

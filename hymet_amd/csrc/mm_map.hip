@@ -1420,9 +1420,28 @@ static int sort_anchor_keys(hymet_ctx *ctx, DevBuf &key, DevBuf &val, int64_t n,
     if (gsort) {
         HY_HIP(out.hb.alloc(head_bits_bytes(n), ctx->stream));
         HY_HIP(out.ax32.alloc(4 * (size_t)n, ctx->stream));
+        // HYMET_ASORT_STATS=1: every batch's block-sort counts on stderr (a measuring aid: it
+        // adds a stream synchronise per batch) -- segments and anchors finished by the outlier
+        // path, segments and anchors that took the full sort
+        static const bool log_stats = [] {
+            const char *e = getenv("HYMET_ASORT_STATS");
+            return e && e[0] == '1';
+        }();
+        DevBuf sstat;
+        if (log_stats) {
+            HY_HIP(sstat.alloc(32, ctx->stream));
+            HY_HIP(hipMemsetAsync(sstat.p, 0, 32, ctx->stream));
+        }
         const int rc = grouped_anchor_sort(ctx, kk, vv, n, d_qoff, n_q, rb, pb, (uint64_t)yhi, max_qlen, kka, vva,
                                            out.ax.as<uint64_t>(), out.ay.as<uint64_t>(), out.hb.as<uint32_t>(),
-                                           out.ax32.as<uint32_t>());
+                                           out.ax32.as<uint32_t>(), log_stats ? sstat.as<unsigned long long>() : nullptr);
+        if (log_stats && rc == HYMET_OK) {
+            unsigned long long h[4] = {};
+            HY_HIP(hipMemcpyAsync(h, sstat.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+            HY_HIP(hipStreamSynchronize(ctx->stream));
+            fprintf(stderr, "[asort] anchors %lld fast_segs %llu fast_anchors %llu full_segs %llu full_anchors %llu\n",
+                    (long long)n, h[0], h[1], h[2], h[3]);
+        }
         if (rc == HYMET_OK) {
             out.has_hb = out.has_x32 = true;
             return HYMET_OK;

@@ -372,6 +372,19 @@ int hymet_emit_paf(hymet_ctx *ctx, const hymet_paf_acc *acc, const uint8_t *d_qn
 int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, int64_t n, int max_dist,
                       int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap,
                       float pen_skip, int32_t *h_f, int64_t *h_p);
+/* The grouped anchor sort alone (the stage inside hymet_mm_map that puts a batch's anchor
+ * keys in minimap2's order), for parity tests: n keys (query | strand | target in rb bits |
+ * target position in pb bits) with values y, query-major, query q's at [h_qoff[q],
+ * h_qoff[q+1]); max_qlen bounds y.  Returns the anchor set in (key, y) order -- h_ax =
+ * strand<<63 | target<<32 | position, h_ay = yhi<<32 | y, h_ax32 = position -- and the head
+ * bitmap h_hb ((n + 31) / 32 words: bit i set where anchor i starts a (query, strand, target)
+ * group).  Returns 1, nothing written, where the grouped sort does not apply (the packed
+ * words would pass 64 bits).  h_stats (nullable, 4 entries): segments and anchors the block
+ * sorts finished by their outlier path, segments and anchors that took their full sort.
+ * Host arrays, synchronous. */
+int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const uint32_t *h_val, int64_t n,
+                         const int64_t *h_qoff, int32_t n_q, int32_t rb, int32_t pb, uint64_t yhi, int64_t max_qlen,
+                         uint64_t *h_ax, uint64_t *h_ay, uint32_t *h_ax32, uint32_t *h_hb, int64_t *h_stats);
 
 /* --------------------------------------------------- weighted LCA (classify)
  * Replaces the per-query loop of scripts/classification_cami.py:290-308 (+ _weighted_lca
