@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <utility>
@@ -69,6 +71,26 @@ constexpr int kMbox = 64;  // mailbox words per context
 inline int64_t *mb_dev(hymet_ctx *c, int i) { return c->mbox_d + i; }
 // host read of mailbox word i, after the stream has been synchronised
 inline int64_t mb_read(const hymet_ctx *c, int i) { return __atomic_load_n(c->mbox_h + i, __ATOMIC_ACQUIRE); }
+}  // namespace hymet
+
+namespace hymet {
+// Environment knobs (tests, A/B timing, diagnostics) are read where they are
+// used, at every call: nothing is cached, so a change of the environment holds from the next
+// call on.  env_str: the value, nullptr when unset or empty.
+inline const char *env_str(const char *name) {
+    const char *e = getenv(name);
+    return e && *e ? e : nullptr;
+}
+// a switch: off when the value starts with '0', on for anything else, dflt when unset
+inline bool env_flag(const char *name, bool dflt = false) {
+    const char *e = env_str(name);
+    return e ? e[0] != '0' : dflt;
+}
+// an integer clamped to [lo, hi]; dflt, as it is, when unset
+inline int64_t env_int(const char *name, int64_t dflt, int64_t lo, int64_t hi) {
+    const char *e = env_str(name);
+    return e ? std::max(lo, std::min(hi, (int64_t)atoll(e))) : dflt;
+}
 }  // namespace hymet
 
 namespace hymet {

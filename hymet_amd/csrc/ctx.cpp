@@ -42,12 +42,8 @@ static void (*g_oom_hook)(void *) = nullptr;
 static void *g_oom_user = nullptr;
 
 static size_t cache_cap() {
-    static const size_t cap = [] {
-        const char *e = getenv("HYMET_SCRATCH_CAP_GB");
-        const double gb = e ? atof(e) : 160.0;
-        return (size_t)(gb * 1073741824.0);
-    }();
-    return cap;
+    const char *e = hymet::env_str("HYMET_SCRATCH_CAP_GB");
+    return (size_t)((e ? atof(e) : 160.0) * 1073741824.0);
 }
 
 static size_t size_class(size_t b) {

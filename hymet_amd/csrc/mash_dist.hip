@@ -222,12 +222,11 @@ struct DistCfg {
     int path = 0, tq = 0;
 };
 DistCfg &cfg() {
-    static DistCfg c = [] {  // the environment is read once
+    static DistCfg c = [] {  // a process-wide setting (hymet_mash_dist_tune): the environment gives its initial value
         DistCfg d;
-        const char *p = getenv("HYMET_DIST_PATH");
+        const char *p = hymet::env_str("HYMET_DIST_PATH");
         if (p && std::string(p) == "global") d.path = 1;
-        const char *t = getenv("HYMET_DIST_TQ");
-        if (t) d.tq = std::max(0, std::min(kMaxTq, atoi(t)));
+        d.tq = (int)hymet::env_int("HYMET_DIST_TQ", d.tq, 0, kMaxTq);
         return d;
     }();
     return c;

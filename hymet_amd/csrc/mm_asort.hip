@@ -876,10 +876,7 @@ int sort_segments(hymet_ctx *ctx, const Seg *lists, int64_t cap, const int32_t *
                   const uint32_t *val, int nbits, int ybits, const AnchorOut &out, unsigned long long *stats) {
     hipStream_t st = ctx->stream;
     // HYMET_ASORT_ADAPT=0: the block sorts without their outlier path (A/B timing, tests)
-    static const int adapt = [] {
-        const char *e = getenv("HYMET_ASORT_ADAPT");
-        return e && e[0] == '0' ? 0 : 1;
-    }();
+    const int adapt = env_flag("HYMET_ASORT_ADAPT", true) ? 1 : 0;
 #define HY_SEG_LAUNCH(cls, kern, block)                                                                                     \
     if (hc[cls] > 0) {                                                                                                      \
         hipLaunchKernelGGL(kern, dim3((unsigned)hc[cls]), dim3(block), 0, st, lists + cls * cap, key, val, nbits, ybits, out, \

@@ -66,85 +66,9 @@ namespace {
 #ifndef HYMET_CHAIN_IDQ
 #define HYMET_CHAIN_IDQ 64
 #endif
-// A colinear batch's pre-batch best B from the O(1) window sources when they decide it.
-#ifndef HYMET_CHAIN_B0FAST
-#define HYMET_CHAIN_B0FAST 1
-#endif
-// Block summaries of colinear blocks (y increasing) by one DPP prefix min and popcounts
-// instead of a shuffle scan and a readlane loop over the records (~64 per colinear block).
-#ifndef HYMET_CHAIN_CBFAST
-#define HYMET_CHAIN_CBFAST 1
-#endif
-// Colinear batch commits: the inner max-deque's records and the tail block's argmin from the
-// batch's monotone values in O(1) when f + span rises and the priority falls along the batch.
-#ifndef HYMET_CHAIN_MONO
-#define HYMET_CHAIN_MONO 1
-#endif
-// Window-start blocks passed whole are skipped by their last x (an LDS ring) instead of loaded.
-#ifndef HYMET_CHAIN_BLX
-#define HYMET_CHAIN_BLX 0
-#endif
-// A batch starts at any anchor whose window best B lies in its range (not only after B = i-1).
-#ifndef HYMET_CHAIN_B0ANY
-#define HYMET_CHAIN_B0ANY 1
-#endif
 // First back-off step of the batch attempts after a failed or short batch.
 #ifndef HYMET_CHAIN_SPEC_GAP0
 #define HYMET_CHAIN_SPEC_GAP0 2
-#endif
-// Inner-window entries leaving as a prefix of the (y, idx) list are popped, not compacted.
-#ifndef HYMET_CHAIN_IPOP
-#define HYMET_CHAIN_IPOP 1
-#endif
-// Colinear batches skip the prefix min of priorities and the prefix max of f + span.
-#ifndef HYMET_CHAIN_BMONO
-#define HYMET_CHAIN_BMONO 1
-#endif
-// Batch f / p global stores issued at the end of the commit instead of its start.
-#ifndef HYMET_CHAIN_LATE_FP
-#define HYMET_CHAIN_LATE_FP 1
-#endif
-// Head cache prefetch: when the head cache takes block b, block b + 1's entries are loaded
-// into registers, so the next window-start block change does not wait on HBM.
-#ifndef HYMET_CHAIN_HCPF
-#define HYMET_CHAIN_HCPF 0
-#endif
-// Lean head cache: when the window start enters a block beyond the ring, load only its x (the
-// window-start probes) and the block's suffix records (kept with its summary), not every
-// entry's (x, y, f, p); entries are fetched in full only when a y-bounded scan needs them.
-#ifndef HYMET_CHAIN_HLEAN
-#define HYMET_CHAIN_HLEAN 0
-#endif
-// Entries fetched from HBM (head cache, window scans, the winner) without p: only the inner
-// walk reads an entry's predecessor, and it fetches through the ring or HBM (fetch_p)
-#ifndef HYMET_CHAIN_HNOP
-#define HYMET_CHAIN_HNOP 1
-#endif
-// A window that anchor i-1 leaves empties whole (x never decreases along a group): st / st_in
-// jump to i and the deques and the inner list are cleared in O(1), instead of one probe round
-// (and a head-cache load beyond the rings) per 64 entries passed.
-#ifndef HYMET_CHAIN_DRAIN
-#define HYMET_CHAIN_DRAIN 1
-#endif
-// A committed batch also inserts its last anchor into the window structures when the next
-// anchor's x differs (lchain.c inserts [i0, i) once x changes): the next iteration then has
-// nothing to insert (step 1 is skipped) instead of one insert_one per batch.
-#ifndef HYMET_CHAIN_INSALL
-#define HYMET_CHAIN_INSALL 1
-#endif
-// A colinear batch is cut at the first anchor whose y does not rise: no anchor from there on
-// can commit (the batch needs py < ky lane to lane), and Y -- the y bound B is taken under --
-// becomes the y of the last anchor that can.  Without the cut, a stray anchor inside the
-// 64-anchor window past a chain's end set Y to its random y, every chain anchor above it
-// failed `ky <= Y`, and the rest of the chain was single-stepped behind the back-off.
-#ifndef HYMET_CHAIN_YPREFIX
-#define HYMET_CHAIN_YPREFIX 1
-#endif
-// Wave-uniform loop state pinned to scalar registers (readfirstlane at the derivation points):
-// branches on it become scalar branches instead of exec-mask bookkeeping (first pass 11.55 ->
-// 11.27 ms, long join 7.27 -> 7.07 ms on the real-anchor dump; VALU -9 % per anchor).
-#ifndef HYMET_CHAIN_UNI
-#define HYMET_CHAIN_UNI 1
 #endif
 #ifndef HYMET_CHAIN_WPE  // waves per SIMD the register allocation targets (0: compiler's choice)
 #define HYMET_CHAIN_WPE 4
@@ -153,10 +77,7 @@ constexpr int kRing = HYMET_CHAIN_RING;  // LDS ring of recent anchors, int4 eac
 constexpr int kRingMask = kRing - 1;
 constexpr int kStair = 4;       // staircase entries kept per block summary
 constexpr int kSumInts = kStair + 1;  // int4 words per block summary: staircase + (ymin, ymax, n|trunc, -)
-// HBM summaries add the block's last kSufRec suffix records: the lanes better than every later
-// lane (the argmins of the suffixes [k, 64)), lane 63 first, as ring entries (x, y, f, pw)
-constexpr int kSufRec = HYMET_CHAIN_HLEAN ? 4 : 0;
-constexpr int kGSumInts = kSumInts + kSufRec;
+constexpr int kGSumInts = kSumInts;  // int4 words per block summary in HBM
 constexpr int kSumRing = HYMET_CHAIN_SUMRING;  // LDS ring of the last complete block summaries (1.25 KB)
 #ifndef HYMET_CHAIN_INNER
 #define HYMET_CHAIN_INNER 256
@@ -165,10 +86,8 @@ constexpr int kInnerCap = HYMET_CHAIN_INNER;  // LDS inner-window list (ring-deq
 constexpr int kXRing = 256;  // LDS ring of the last 256 anchors' x (1 KB): the window-start probes
 constexpr int kBdq = HYMET_CHAIN_BDQ;  // block-argmin deque, 2 int4 per element (1 KB)
 constexpr int kIdq = HYMET_CHAIN_IDQ;  // inner max-deque (idx, f + span) (0.5 KB)
-constexpr int kBlx = 64;  // LDS ring of the last 64 complete blocks' last x (0.25 KB)
 constexpr size_t kChainLds = kRing * sizeof(int4) + kSumRing * kSumInts * sizeof(int4) + 64 * 2 * sizeof(int4) +
-                             kInnerCap * sizeof(int2) + kXRing * sizeof(int32_t) + kBdq * 2 * sizeof(int4) + kIdq * sizeof(int2) +
-                             (HYMET_CHAIN_BLX ? kBlx * sizeof(int32_t) : 0);
+                             kInnerCap * sizeof(int2) + kXRing * sizeof(int32_t) + kBdq * 2 * sizeof(int4) + kIdq * sizeof(int2);
 constexpr int kNegInf = -(1 << 29);
 constexpr int kSpecGap0 = HYMET_CHAIN_SPEC_GAP0;
 
@@ -464,31 +383,13 @@ struct Ent {
 };
 
 __device__ __forceinline__ int rl(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-#if HYMET_CHAIN_UNI
+// Wave-uniform loop state is pinned to scalar registers (readfirstlane at the derivation points):
+// branches on it become scalar branches instead of exec-mask bookkeeping (first pass 11.55 ->
+// 11.27 ms, long join 7.27 -> 7.07 ms on the real-anchor dump; VALU -9 % per anchor).
 __device__ __forceinline__ int32_t U(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ double Ud(double v) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
-#else
-__device__ __forceinline__ int32_t U(int32_t v) { return v; }
-__device__ __forceinline__ double Ud(double v) { return v; }
-#endif
-// HYMET_CHAIN_UNI2: values every lane loads from the same LDS word (deque ends, list ends, the
-// head suffix record, entries passed to insert_one) are wave-uniform but look divergent to the
-// compiler, which then keeps the loop state derived from them (deque indices, list length) in
-// VGPRs and runs their loops under exec masks; readfirstlane makes them SGPRs
-#ifndef HYMET_CHAIN_UNI2
-#define HYMET_CHAIN_UNI2 0
-#endif
-#if HYMET_CHAIN_UNI2
-__device__ __forceinline__ int32_t UL(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int4 UL4(int4 v) { return make_int4(UL(v.x), UL(v.y), UL(v.z), UL(v.w)); }
-__device__ __forceinline__ int2 UL2(int2 v) { return make_int2(UL(v.x), UL(v.y)); }
-#else
-__device__ __forceinline__ int32_t UL(int32_t v) { return v; }
-__device__ __forceinline__ int4 UL4(int4 v) { return v; }
-__device__ __forceinline__ int2 UL2(int2 v) { return v; }
-#endif
 __device__ __forceinline__ double rld(double v, int l) {
     return __hiloint2double(rl(__double2hiint(v), l), rl(__double2loint(v), l));
 }
@@ -511,9 +412,6 @@ __device__ __forceinline__ double st_pr(const int4 &v) { return __hiloint2double
 #define HYMET_CHAIN_MID 64
 #endif
 // chain_mid_group skips the inner walk when no inner-tree entry's f + span exceeds max_f
-#ifndef HYMET_CHAIN_MIDSKIP
-#define HYMET_CHAIN_MIDSKIP 1
-#endif
 constexpr int kMidMax = HYMET_CHAIN_MID;
 
 // mg_lchain_rmq on one group of n <= 64 anchors, lane l = anchor l (lchain.c; the same
@@ -580,7 +478,6 @@ __device__ __forceinline__ void chain_mid_group(const ChainParams &P, int64_t g0
                                               __builtin_amdgcn_readlane(SP, bj), P.pen_gap, P.pen_skip, &exact, &width);
             if (width <= P.bw && sc > max_f) max_f = sc, max_j = bj;
             bool walk = !exact && in_in != 0 && yi > 0;
-#if HYMET_CHAIN_MIDSKIP
             // a candidate scores at most f_j + span_j (comput_sc <= the candidate's span), so
             // when no inner-tree entry reaches past max_f the walk changes nothing (its t[]
             // stamps only matter within this iteration) -- the wave kernel's max-deque test
@@ -588,7 +485,6 @@ __device__ __forceinline__ void chain_mid_group(const ChainParams &P, int64_t g0
                 const int ub = __builtin_amdgcn_readlane(scan_max((in_in >> lane & 1) ? F + SP : INT32_MIN), 63);
                 if (ub <= max_f) walk = false;
             }
-#endif
             if (walk) {
                 // inner walk: tree entries with y <= yi - 1 by (y, idx) descending, down to
                 // yi - max_dist_inner -- in walk lanes, a prefix scan of the sequential loop
@@ -626,7 +522,6 @@ __device__ __forceinline__ void chain_mid_group(const ChainParams &P, int64_t g0
     if (act) {
         P.f[g0 + lane] = F;
         P.p[g0 + lane] = PJ < 0 ? -1 : g0 + PJ;
-        if (HYMET_CHAIN_TZERO) P.t_global[g0 + lane] = 0;  // the backtrack's marks start cleared
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -659,7 +554,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
     sp += kIdq * sizeof(int2);
     int32_t *xring = reinterpret_cast<int32_t *>(sp);  // x of anchor j at [j & (kXRing - 1)]
     sp += kXRing * sizeof(int32_t);
-    int32_t *blx = reinterpret_cast<int32_t *>(sp);  // x of block b's last anchor at [b & (kBlx - 1)]
     const double c = 0.5 * (double)P.pen_gap;
     const int32_t n_work = P.work_end ? min(P.n_work, *P.work_end) : P.n_work;
     // work list dealt over kChainStripes counters on separate lines (stripe s: positions
@@ -691,8 +585,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
         int4 *gsum = P.sum + ((g0 >> 6) + g) * kGSumInts;
         int32_t hb = -1;        // block held by the head cache
         bool hsuf_ok = false;   // hsuf holds the suffix argmins of block hb
-        uint64_t hmask = ~0ull;  // lanes of block hb whose full entry is in hc (x always is)
-        int32_t hlow = 0;        // hsuf is valid for the suffixes [k, 64), k >= hlow
         int32_t i = 0;
         CPROF_DECL
         // anchor jl (local) as seen at iteration i: ring [i - kRing, i), head cache, else HBM
@@ -701,26 +593,19 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             int4 v;
             if (i - jl <= kRing) {
                 v = ring[jl & kRingMask];
-            } else if ((jl >> 6) == hb && (hmask >> (jl & 63) & 1)) {
+            } else if ((jl >> 6) == hb) {
                 v = hc[jl & 63];
             } else {
                 CCOUNT(0);
                 const int32_t x = P.ax[g0 + jl];
                 const uint64_t y = P.ay[g0 + jl];
-#if HYMET_CHAIN_HNOP
                 v = make_int4(x, (int32_t)y, ld_l2(P.f + g0 + jl), (int32_t)((uint32_t)(y >> 32 & 0xff) << 24));
-#else
-                const int64_t pp = ld_l2(P.p + g0 + jl);
-                v = make_int4(x, (int32_t)y, ld_l2(P.f + g0 + jl),
-                              (int32_t)((pp < 0 ? 0u : (uint32_t)(pp - g0 + 1)) | (uint32_t)(y >> 32 & 0xff) << 24));
-#endif
             }
             e.x = v.x, e.y = v.y, e.f = v.z, e.pw = v.w;
             return e;
         };
         // the same with p (the inner walk): the ring, else HBM -- head-cache entries carry no p
         auto fetch_p = [&](int32_t jl) -> Ent {
-#if HYMET_CHAIN_HNOP
             Ent e;
             int4 v;
             if (i - jl <= kRing) {
@@ -734,9 +619,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             }
             e.x = v.x, e.y = v.y, e.f = v.z, e.pw = v.w;
             return e;
-#else
-            return fetch(jl);
-#endif
         };
         // x of anchor jl (local) at iteration i, for the window-start probes: the x ring (last
         // kXRing anchors), the head cache, else a plain load of ax
@@ -747,38 +629,11 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
         };
         auto fetch_y = [&](int32_t jl) -> int32_t {
             if (i - jl <= kRing) return ring[jl & kRingMask].y;
-            if ((jl >> 6) == hb && (hmask >> (jl & 63) & 1)) return hc[jl & 63].y;
+            if ((jl >> 6) == hb) return hc[jl & 63].y;
             return (int32_t)P.ay[g0 + jl];
         };
         int32_t i0 = 0, st = 0, st_in = 0;
         bool t_used = false;  // the overflow walk stamped t_global
-        // head-cache prefetch (HYMET_CHAIN_HCPF: 1 both passes, 2 the long join only): when the
-        // head cache takes block b, block b + 1's x, y, f are loaded into registers (p-less, as
-        // every HBM entry fetch), so the next window-start block change does not wait on HBM
-        constexpr bool kHcpf = HYMET_CHAIN_HCPF == 1 || (HYMET_CHAIN_HCPF == 2 && kLongPass);
-        static_assert(!kHcpf || HYMET_CHAIN_HNOP, "the prefetched head entries carry no p");
-        int32_t pfb = -1, pf_x = 0, pf_ylo = 0, pf_yhi = 0, pf_f = 0;  // block pfb's entries (lane l: entry l)
-        auto hc_take = [&](int32_t b) -> Ent {  // entry (b << 6) + lane for the head cache
-            if constexpr (!kHcpf) {
-                return fetch((b << 6) + lane);
-            } else {
-                Ent e;
-                if (b == pfb) {
-                    e.x = pf_x, e.y = pf_ylo, e.f = pf_f;
-                    e.pw = (int32_t)(((uint32_t)pf_yhi & 0xff) << 24);
-                } else {
-                    e = fetch((b << 6) + lane);
-                }
-                const int32_t jn = ((b + 1) << 6) + lane;
-                if (((b + 1) << 6) + 63 < i0) {
-                    const int32_t *ay32 = reinterpret_cast<const int32_t *>(P.ay + g0 + jn);
-                    pf_x = P.ax[g0 + jn], pf_ylo = ay32[0], pf_yhi = ay32[1];
-                    pf_f = ld_l2(P.f + g0 + jn);
-                    pfb = b + 1;
-                }
-                return e;
-            }
-        };
         auto sum_at = [&](int32_t b, int k) -> int4 {  // word k of block b's summary
             if ((i0 >> 6) - b <= kSumRing) return ssum[(b & (kSumRing - 1)) * kSumInts + k];
             return ld_l2(gsum + (int64_t)b * kGSumInts + k);
@@ -800,15 +655,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     }
                 }
             };
-#if HYMET_CHAIN_HLEAN
-            if (st < (fb << 6) && (st >> 6) == hb && hmask != ~0ull) {  // lean head cache: load it in full
-                const Ent e = fetch((hb << 6) + lane);
-                __builtin_amdgcn_wave_barrier();
-                hc[lane] = make_int4(e.x, e.y, e.f, e.pw);
-                __builtin_amdgcn_wave_barrier();
-                hmask = ~0ull;
-            }
-#endif
             if (st < (fb << 6)) scan(st, min(fb << 6, i0));             // head
             if (fe >= fb && (fe << 6) < i0) scan(max(fe << 6, st), i0);  // tail
             for (int32_t base = fb; base < fe; base += 64) {
@@ -853,7 +699,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
         auto L = [&](int k) -> int2 & { return lst[(lh + k) & (kInnerCap - 1)]; };
         auto reload_ends = [&]() {
             if (ni > 0) {
-                const int2 a = UL2(L(0)), b = UL2(L(ni - 1));
+                const int2 a = L(0), b = L(ni - 1);
                 lfy = a.x, lfj = a.y, lby = b.x, lbj = b.y;
             }
         };
@@ -901,36 +747,15 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             // its rank is the number of records in higher lanes, and the y range is lanes 0, 63
             const int32_t ynx = down1(e.y);
             if (__ballot(lane == 63 || e.y < ynx) == ~0ull) {
-#if HYMET_CHAIN_CBFAST
-#if HYMET_CHAIN_BMONO
                 // priorities non-increasing along the block (a colinear chain): every lane is
                 // its prefix's best, no scan needed
                 const double plp = __hiloint2double(shr1(__double2hiint(pl), __double2hiint(pl)), shr1(__double2loint(pl), __double2loint(pl)));
                 if (__ballot(!(plp < pl)) == ~0ull) rec = true;
                 else
-#endif
                 rec = scan_min_d(pl) == pl;
                 recm = __ballot(rec);
                 rank = __popcll(lane == 63 ? 0ull : recm >> (lane + 1));
                 ymn = rl(e.y, 0), ymx = rl(e.y, 63);
-#else
-                double bp = pl;
-                int32_t bj = jl;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const double op = __shfl_up(bp, d, 64);
-                    const int32_t oj = __shfl_up(bj, d, 64);
-                    if (lane >= d && better(op, oj, bp, bj)) bp = op, bj = oj;
-                }
-                rec = bj == jl;
-                recm = __ballot(rec);
-                for (uint64_t m = recm; m;) {
-                    const int k = __ffsll((unsigned long long)m) - 1;
-                    m &= m - 1;
-                    rank += rl(e.y, k) > e.y;
-                }
-                wave_minmax(ymn, ymx);
-#endif
             } else {
                 for (int k = 0; k < 64; ++k) {
                     const int32_t yk = rl(e.y, k);
@@ -946,33 +771,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                 wave_minmax(ymn, ymx);
             }
             const int nrec = __popcll(recm);
-            int32_t mw = 0;
-#if HYMET_CHAIN_HLEAN
-            // suffix records: lane l is one iff it beats every lane > l (ties -> larger index);
-            // priorities non-increasing along the block leave lane 63 alone.  meta.w: lanes of
-            // slots 1..3 (6 bits each), the slot count (bits 18..20) and the lowest lane whose
-            // suffix the kept slots cover (bits 21..26)
-            uint64_t srm = 1ull << 63;
-            if (__ballot(lane == 63 || !(pl < down1d(pl))) != ~0ull) {
-                double sp_ = pl;
-                int32_t sj = jl, sy = e.y;
-                suffix_argmin(sp_, sj, sy);
-                srm = __ballot(sj == jl);
-            }
-            const int sslot = __popcll(lane == 63 ? 0ull : srm >> (lane + 1));  // records above this lane
-            {
-                uint64_t m = srm & ~(1ull << 63);
-                int ns = 1;
-                for (; m && ns < kSufRec; ++ns) {
-                    const int l = 63 - __clzll((long long)m);
-                    m &= ~(1ull << l);
-                    mw |= l << (6 * (ns - 1));
-                }
-                mw |= ns << 18;
-                if (m) mw |= (64 - __clzll((long long)m)) << 21;
-            }
-#endif
-            const int4 meta = make_int4(ymn, ymx, min(nrec, kStair) | (nrec > kStair ? 256 : 0), mw);
+            const int4 meta = make_int4(ymn, ymx, min(nrec, kStair) | (nrec > kStair ? 256 : 0), 0);
             int4 *ls = ssum + (b & (kSumRing - 1)) * kSumInts;
             int4 *gs = gsum + (int64_t)b * kGSumInts;
             __builtin_amdgcn_wave_barrier();
@@ -980,13 +779,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                 ls[rank] = pack_st(pl, jl, e.y);
                 gs[rank] = pack_st(pl, jl, e.y);
             }
-#if HYMET_CHAIN_HLEAN
-            if ((srm >> lane & 1) && sslot < kSufRec) gs[kSumInts + sslot] = make_int4(e.x, e.y, e.f, e.pw);
-#endif
             if (lane == 0) ls[kStair] = meta, gs[kStair] = meta;
-#if HYMET_CHAIN_BLX
-            if (lane == 63) blx[b & (kBlx - 1)] = e.x;
-#endif
             __builtin_amdgcn_wave_barrier();
             if (!bok) return;
             const int l0 = __ffsll((unsigned long long)__ballot(rec && rank == 0)) - 1;
@@ -995,7 +788,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             while (bt > bh && better(apr, aj, bb_pr, bb_j)) {
                 --bt;
                 if (bt > bh) {
-                    const int4 v = UL4(bdq[((bt - 1) & (kBdq - 1)) * 2]);
+                    const int4 v = bdq[((bt - 1) & (kBdq - 1)) * 2];
                     bb_pr = st_pr(v), bb_j = v.z;
                 }
             }
@@ -1014,9 +807,8 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             AMARK(cb_end);
         };
         // entry j (now final) enters the window: inner list, inner max-deque, tail argmin
-        auto insert_one = [&](int32_t j, const Ent ej_in) {
+        auto insert_one = [&](int32_t j, const Ent ej) {
             AMARK(ins_begin);
-            const Ent ej{UL(ej_in.x), UL(ej_in.y), UL(ej_in.f), UL(ej_in.pw)};
             if (P.max_dist_inner > 0) {
                 if (!overflow && ni >= kInnerCap) overflow = true;
                 if (!overflow) {
@@ -1062,7 +854,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     const int32_t v = ej.f + ej.sp();
                     while (it > ih && ib_v <= v) {
                         --it;
-                        if (it > ih) ib_v = UL(idq[(it - 1) & (kIdq - 1)].y);
+                        if (it > ih) ib_v = idq[(it - 1) & (kIdq - 1)].y;
                     }
                     if (it - ih >= kIdq) {
                         iok = false;
@@ -1119,7 +911,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             int32_t max_f = span_i;
             int32_t max_j = -1;
             // ---- 1. i0 advances: insert [i0, i) into the window structures
-#if HYMET_CHAIN_DRAIN
             // x never decreases along a group: when anchor i-1 is beyond max_dist of anchor i,
             // every entry before i is, so both windows empty at once -- [i0, i) is not inserted
             // (it would leave again at step 2), st / st_in jump to i and the deques and the
@@ -1136,7 +927,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                 ih = it;
                 iok = true;
             }
-#endif
             if (i0 < i && prev.x != xi) {
                 for (int32_t j = i0; j < i; ++j) insert_one(j, j == i - 1 ? prev : fetch(j));
                 i0 = i;
@@ -1156,62 +946,16 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     if (hchg) CCOUNT(21);
                     hchg = true;
 #endif
-#if HYMET_CHAIN_HLEAN
-                    // x of every entry and the block's suffix records (lanes 1..4: slots 0..3,
-                    // lane 0: the summary's meta word); the suffix argmins come from the records
-                    const int32_t xl = ldx((hb2 << 6) + lane);
-                    const int4 *gw = gsum + (int64_t)hb2 * kGSumInts + kStair;
-                    const int4 w = ld_l2(gw + min(lane, kSufRec));
-                    const uint32_t mw = (uint32_t)rl(w.w, 0);
-                    {
-                        const int nr = mw >> 18 & 7;
-                        int4 rv = make_int4(rl(w.x, 1), rl(w.y, 1), rl(w.z, 1), rl(w.w, 1));
-                        int32_t rlane = 63;
-                        uint64_t msk = 1ull << 63;
-#pragma unroll
-                        for (int s = 1; s < kSufRec; ++s) {
-                            if (nr > s) {
-                                const int ls = mw >> (6 * (s - 1)) & 63;
-                                msk |= 1ull << ls;
-                                if (ls >= lane) rv = make_int4(rl(w.x, 1 + s), rl(w.y, 1 + s), rl(w.z, 1 + s), rl(w.w, 1 + s)), rlane = ls;
-                            }
-                        }
-                        const double rp = prio(rv.z, rv.x, rv.y, c);
-                        __builtin_amdgcn_wave_barrier();
-                        hc[lane] = rlane == lane ? rv : make_int4(xl, 0, 0, 0);
-                        hsuf[lane] = pack_st(rp, (hb2 << 6) + rlane, rv.y);
-                        __builtin_amdgcn_wave_barrier();
-                        hb = hb2;
-                        hmask = msk;
-                        hlow = mw >> 21 & 63;  // hsuf holds the suffixes from lane hlow on
-                        hsuf_ok = true;
-                        return;
-                    }
-#endif
-                    const Ent e = hc_take(hb2);
+                    const Ent e = fetch((hb2 << 6) + lane);
                     __builtin_amdgcn_wave_barrier();
                     hc[lane] = make_int4(e.x, e.y, e.f, e.pw);
                     __builtin_amdgcn_wave_barrier();
                     hb = hb2;
-                    hmask = ~0ull;
-                    hlow = 0;
                     hsuf_ok = false;
                 }
             };
             for (;;) {
                 if (st >= i) break;
-#if HYMET_CHAIN_BLX
-                // complete blocks the window start passes whole (their last anchor does, and x
-                // never decreases) are skipped by that anchor's x, without loading them; only
-                // the block the start stops in is cached
-                while ((st & 63) == 0 && (st >> 6) < (i0 >> 6) && (i0 >> 6) - (st >> 6) <= kBlx) {
-                    const int32_t xl = blx[(st >> 6) & (kBlx - 1)];
-                    if (!((int64_t)(uint32_t)xi > (int64_t)(uint32_t)xl + P.max_dist || i0 - (st | 63) > P.cap_rmq_size)) break;
-                    st += 64;
-                }
-                if (st >= i) break;
-                head_take();
-#endif
                 const int32_t bend = min(i, ((st >> 6) + 1) << 6);
                 const int32_t j = st + lane;
                 bool adv = false;
@@ -1220,41 +964,35 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                 const int t = ~m ? __ffsll((unsigned long long)~m) - 1 : 64;  // lanes [0, t) advance
                 st += min(t, bend - st);
                 if (st < bend) break;
-#if !HYMET_CHAIN_BLX
                 head_take();
-#endif
             }
             const int32_t fb = (st + 63) >> 6, fe = i0 >> 6;  // complete window blocks [fb, fe)
             while (bt > bh && (bf_j >> 6) < fb) {
                 ++bh;
                 if (bt > bh) {
-                    const int4 v = UL4(bdq[(bh & (kBdq - 1)) * 2]);
+                    const int4 v = bdq[(bh & (kBdq - 1)) * 2];
                     bf_pr = st_pr(v), bf_j = v.z, bf_y = v.w;
-                    bf_e = UL4(bdq[(bh & (kBdq - 1)) * 2 + 1]);
+                    bf_e = bdq[(bh & (kBdq - 1)) * 2 + 1];
                 }
             }
-            if ((st & 63) && (st >> 6) < fe && ((st >> 6) != hb || !hsuf_ok || (st & 63) < hlow)) {
+            if ((st & 63) && (st >> 6) < fe && ((st >> 6) != hb || !hsuf_ok)) {
                 // partial head block: cache it with its suffix argmins [lane, 64)
                 CCOUNT(5);
                 const int32_t b = st >> 6, j = (b << 6) + lane;
                 const Ent e = fetch(j);
                 double pr = prio(e.f, e.x, e.y, c);
                 int32_t pj = j, py = e.y;
-#if HYMET_CHAIN_MONO
                 // priorities non-increasing along the block: every suffix's argmin is lane 63
                 const double pnx = down1d(pr);
                 if (__ballot(lane == 63 || !(pr < pnx)) == ~0ull) {
                     pr = rld(pr, 63), pj = (b << 6) + 63, py = rl(e.y, 63);
                 } else
-#endif
                     suffix_argmin(pr, pj, py);
                 __builtin_amdgcn_wave_barrier();
                 hc[lane] = make_int4(e.x, e.y, e.f, e.pw);
                 hsuf[lane] = pack_st(pr, pj, py);
                 __builtin_amdgcn_wave_barrier();
                 hb = b;
-                hmask = ~0ull;
-                hlow = 0;
                 hsuf_ok = true;
             }
             CPROF(1);
@@ -1271,7 +1009,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     if (t > 1 && !overflow && ni > 0) {
                         // several entries leave: stable compaction of the list keeps j >= st_in + t
                         const int32_t lim = st_in + t;
-#if HYMET_CHAIN_IPOP
                         // the list holds exactly the entries [st_in, i0), so when its first nl
                         // entries all leave they are the nl leaving ones (colinear: lowest y and
                         // index together) and are popped from the front
@@ -1282,7 +1019,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                                 lh = (lh + nl) & (kInnerCap - 1);
                                 ni -= nl;
                                 if (ni > 0) {
-                                    const int2 a = UL2(L(0));
+                                    const int2 a = L(0);
                                     lfy = a.x, lfj = a.y;
                                 }
                                 st_in += t;
@@ -1290,7 +1027,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                                 continue;
                             }
                         }
-#endif
                         int kept = 0;
                         for (int base = 0; base < ni; base += 64) {
                             const int kk = base + lane;
@@ -1319,7 +1055,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                             lh = (lh + 1) & (kInnerCap - 1);
                             ni--;
                             if (ni > 0) {
-                                const int2 a = UL2(L(0));
+                                const int2 a = L(0);
                                 lfy = a.x, lfj = a.y;
                             }
                             continue;
@@ -1361,9 +1097,9 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     st_in += t;
                     if (t < 64) break;
                 }
-                while (it > ih && UL(idq[ih & (kIdq - 1)].x) < st_in) {
+                while (it > ih && idq[ih & (kIdq - 1)].x < st_in) {
                     ++ih;
-                    if (it > ih) if_v = UL(idq[ih & (kIdq - 1)].y);
+                    if (it > ih) if_v = idq[ih & (kIdq - 1)].y;
                 }
             }
             CPROF(6);
@@ -1394,7 +1130,11 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                 double b0p = 0.0;
                 int32_t b0j = -1;
                 int32_t batch_y = INT32_MAX;  // B's y bound: every committed anchor must lie at or below it
-#if HYMET_CHAIN_YPREFIX
+                // the batch is cut at the first anchor whose y does not rise: no anchor from there on
+                // can commit (the batch needs py < ky lane to lane), and Y -- the y bound B is taken
+                // under -- becomes the y of the last anchor that can.  Without the cut a stray anchor
+                // past a chain's end set Y to its random y, every chain anchor above it failed
+                // `ky <= Y`, and the rest of the chain was single-stepped behind the back-off.
                 if (!kLongPass && walk_ok && Lb >= 2) {  // the long join's chained anchors rarely break y order
                     const int offy = (i - cb) + lane;
                     const int32_t ylo_ = __shfl((int32_t)cy, offy & 63, 64), yhi_ = __shfl((int32_t)ny, offy & 63, 64);
@@ -1403,12 +1143,10 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     const uint64_t brk = __ballot(lane >= 1 && lane < Lb && !(yp < yl));
                     if (brk) Lb = __ffsll((unsigned long long)brk) - 1;
                 }
-#endif
                 if (walk_ok && Lb >= 2) {
                     const int offl = (i - cb) + Lb - 1;
                     const int32_t ymax = (int32_t)(offl < 64 ? rl((int32_t)cy, offl) : rl((int32_t)ny, offl - 64));
                     batch_y = ymax;
-#if HYMET_CHAIN_B0FAST
                     // the window's best ignoring y (head suffix, block deque front, tail argmin:
                     // the O(1) sources step 4 uses) is B when its y <= Y -- the colinear case;
                     // only otherwise scan the block summaries
@@ -1417,7 +1155,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     int32_t gj = -1, gy = 0;
                     if (cert) {
                         if (st < (fb << 6)) {
-                            const int4 v = UL4(hsuf[st & 63]);
+                            const int4 v = hsuf[st & 63];
                             gp = st_pr(v), gj = v.z, gy = v.w;
                         }
                         if (fb < fe) {
@@ -1428,23 +1166,17 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     }
                     if (cert && gj >= 0 && gy <= ymax) b0p = gp, b0j = gj;
                     else
-#endif
                     window_best(ymax == INT32_MAX ? ymax : ymax + 1, INT32_MIN, false, b0p, b0j);
                 }
                 CCOUNT(8);
                 GCNT(y, 1);
                 if (b0j != i - 1) CCOUNT(10);
                 if (!walk_ok) CCOUNT(11);
-#if HYMET_CHAIN_B0ANY
                 // the batch's first anchor takes B as its predecessor (B is the best entry of its
                 // krmq range whenever it lies in that range: checked with the others below), so a
                 // batch also starts right after an anchor that chained elsewhere
                 if (b0j >= 0 && walk_ok && Lb >= 2) {
                     const Ent e0 = b0j == i - 1 ? prev : fetch(b0j);
-#else
-                if (b0j == i - 1 && walk_ok && Lb >= 2) {
-                    const Ent e0 = prev;
-#endif
                     AMARK(batch_begin);
                     // anchors k = i + lane from the chunk registers (cx: [cb, cb+64), nx: next 64)
                     const int off = (i - cb) + lane;
@@ -1471,7 +1203,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     // priorities of batch entries; the candidate of lane l is entry l-1
                     const double pk = prio(fk, kx, ky, c);
                     const int vk = inb ? fk + ksp : INT32_MIN;
-#if HYMET_CHAIN_BMONO
                     // a colinear batch: priorities fall and f + span rises along it, so each
                     // prefix min / max is the lane's own value and the two scans are skipped
                     // (lanes past the batch only feed lanes that fail `inb`)
@@ -1481,10 +1212,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     int vmx = vk;
                     if (!bmono) ipm = scan_min_d(inb ? pk : 1e300), vmx = scan_max(vk);
                     const int vex = shr1(vmx, INT32_MIN);  // max over the entries before k
-#else
-                    const double ipm = scan_min_d(inb ? pk : 1e300);
-                    const int vex = shr1(scan_max(vk), INT32_MIN);  // max over the entries before k
-#endif
                     const bool best_here = pk == ipm && !(b0p < pk);  // beats B0 and earlier entries
                     // (cross-lane operations run with every lane active: DPP reads of an
                     // inactive lane return the fallback value)
@@ -1547,7 +1274,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     }
                     AMARK(batch_verified);
                     if (acc > 0) {
-#if HYMET_CHAIN_INSALL
                         // the anchor after the batch (lane acc, or the next chunk for a full batch):
                         // a different x lets the last committed entry enter the window now
                         bool ins_all = false;
@@ -1556,9 +1282,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                             const int32_t xn = acc < 64 ? rl(kx, acc) : rl(nx, offn - 64);
                             ins_all = xn != rl(kx, acc - 1) && rl(gap_own ? 1 : 0, acc - 1) != 0;
                         }
-#else
-                        const bool ins_all = false;
-#endif
                         // the next iteration's chunks first: nothing below reads the chunk
                         // registers, and the rotation then waits on no store of this commit
                         advance(i + acc);
@@ -1567,11 +1290,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                         const int32_t pk_local = linked ? (lane == 0 ? b0j : k - 1) : -1;
                         const int32_t pw = (int32_t)((uint32_t)(pk_local + 1) | (uint32_t)ksp << 24);
                         if (lane < acc) {
-#if !HYMET_CHAIN_LATE_FP
-                            P.f[g0 + k] = fk;
-                            P.p[g0 + k] = pk_local < 0 ? -1 : g0 + pk_local;
-                            if (HYMET_CHAIN_TZERO) P.t_global[g0 + k] = 0;
-#endif
                             ring[k & kRingMask] = make_int4(kx, ky, fk, pw);
                             xring[k & (kXRing - 1)] = kx;
                         }
@@ -1601,7 +1319,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                                 const int v = fk + ksp;
                                 int run = lane < nins ? v : INT32_MIN;
                                 int sfx;
-#if HYMET_CHAIN_MONO
                                 // f + span increasing along the batch (colinear): the last entry
                                 // is the only record and the maximum
                                 const int vnx = down1(v);
@@ -1609,7 +1326,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                                     run = rl(v, nins - 1);
                                     sfx = lane < nins - 1 ? run : INT32_MIN;
                                 } else
-#endif
                                 {
                                     run = suffix_max(run);
                                     sfx = down1(run);
@@ -1618,7 +1334,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                                 const int vmax = rl(run, 0);
                                 while (it > ih && ib_v <= vmax) {
                                     --it;
-                                    if (it > ih) ib_v = UL(idq[(it - 1) & (kIdq - 1)].y);
+                                    if (it > ih) ib_v = idq[(it - 1) & (kIdq - 1)].y;
                                 }
                                 const bool recd = lane < nins && v > sfx;
                                 const uint64_t rm = __ballot(recd);
@@ -1637,7 +1353,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                             // tail-block argmin, and blocks completed by the insertions
                             const int32_t nb0 = i >> 6, nb1 = (i + nins) >> 6;
                             for (int32_t b = nb0; b < nb1; ++b) complete_block(b);
-#if HYMET_CHAIN_MONO
                             // the last inserted entry is the batch's prefix minimum (priorities fall
                             // along a colinear chain): it is the argmin of any suffix of the batch,
                             // so the tail block's argmin is it (or the old tail's, no block completed)
@@ -1649,7 +1364,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                                 if (nb1 > nb0 || (i & 63) == 0 || t_j < 0 || !(t_pr < pl_last))
                                     t_pr = pl_last, t_j = i + nins - 1, t_y = rl(ky, nins - 1);
                             } else
-#endif
                             {
                                 const int32_t tb = (i + nins) & ~63, j = tb + lane;
                                 double tp = 0.0;
@@ -1664,15 +1378,12 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                             i0 = i + nins;
                         }
                         const int l = acc - 1;
-#if HYMET_CHAIN_LATE_FP
                         // the batch's f / p stores go last: a vector-memory wait inside the commit
                         // (e.g. a spill reload) would otherwise wait for them too (vmcnt is in order)
                         if (lane < acc) {
                             P.f[g0 + k] = fk;
                             P.p[g0 + k] = pk_local < 0 ? -1 : g0 + pk_local;
-                            if (HYMET_CHAIN_TZERO) P.t_global[g0 + k] = 0;
                         }
-#endif
                         prev.x = rl(kx, l), prev.y = rl(ky, l), prev.f = rl(fk, l), prev.pw = rl(pw, l);
                         i += acc;
                         AMARK(batch_end);
@@ -1694,7 +1405,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                 int32_t wy = 0, src = -1;
                 if (cert) {
                     if (st < (fb << 6)) {  // partial head block (complete, cached with suffix argmins)
-                        const int4 v = UL4(hsuf[st & 63]);
+                        const int4 v = hsuf[st & 63];
                         bp = st_pr(v), bj = v.z, wy = v.w, src = 0;
                     }
                     if (fb < fe) {
@@ -1822,7 +1533,6 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             // stamps only ever land on earlier anchors, and are cleared at the group's end)
             P.f[g0 + i] = max_f;
             P.p[g0 + i] = max_j < 0 ? -1 : g0 + max_j;
-            if (HYMET_CHAIN_TZERO) P.t_global[g0 + i] = 0;
             prev.x = xi, prev.y = yi, prev.f = max_f, prev.pw = (int32_t)((uint32_t)(max_j + 1) | (uint32_t)span_i << 24);
             if (lane == 0) {
                 ring[i & kRingMask] = make_int4(prev.x, prev.y, prev.f, prev.pw);
@@ -1865,7 +1575,7 @@ struct BacktrackParams {
 // reversed).  Path nodes are marked as the walk passes them and the few past the best end
 // unmarked afterwards, so no pass re-reads the path.  t after the backtrack: 0 = free, 1 = used
 // by a walk whose chain was dropped (score or count below the minimum), 2 = in a kept chain
-// (the long join reads the 2s of its queries, mm_map.hip mark_count / mark_compact).
+// (the long join reads the 2s of its queries, mm_chainset.hip mark_count / mark_compact).
 // Paths run mostly down consecutive anchors, so the walk keeps a
 // window of kBtWin (p, f, t) triples below the current node, loaded together (one memory
 // round trip per window instead of one per step); the z scan batches its t probes the same
@@ -1903,12 +1613,7 @@ constexpr int kBtChunks = HYMET_BT_CHUNKS;
 #ifndef HYMET_BT_PROBE
 #define HYMET_BT_PROBE 4
 #endif
-constexpr int kBtProbe = HYMET_BT_PROBE;
-// Starts whose predecessor is already used are settled from the probe's prefetched t / f of
-// that predecessor, without a walk (no window load, no mark re-read).
-#ifndef HYMET_BT_TRIV
-#define HYMET_BT_TRIV 1
-#endif  // z probe block: kBtProbe * 64 entries
+constexpr int kBtProbe = HYMET_BT_PROBE;  // z probe block: kBtProbe * 64 entries
 
 __device__ __forceinline__ int32_t uni(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int64_t uni64(int64_t v) {
@@ -1991,9 +1696,7 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
         int64_t zrem = z1 - z0;
         int32_t zc[kBtProbe], tv[kBtProbe], zfv[kBtProbe];
         int64_t zpv[kBtProbe];  // f and p of the entries that read unmarked: a walk's start
-#if HYMET_BT_TRIV
         int32_t tqv[kBtProbe], fqv[kBtProbe];  // t and f of their predecessors (t as read at the probe)
-#endif
         bool stale = false;
         while (k >= z0 && zrem > 0) {
             if (ptop < 0 || k <= ptop - 64 * kBtProbe) {
@@ -2015,14 +1718,12 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
                     zfv[c] = tv[c] == 0 ? P.f[zc[c]] : 0;
                     zpv[c] = tv[c] == 0 ? P.p[zc[c]] : -1;
                 }
-#if HYMET_BT_TRIV
 #pragma unroll
                 for (int c = 0; c < kBtProbe; c++) {
                     const bool q = tv[c] == 0 && zpv[c] >= 0;
                     tqv[c] = q ? ld_l2(P.t + zpv[c]) : 0;
                     fqv[c] = q ? P.f[zpv[c]] : 0;
                 }
-#endif
             } else if (stale) {  // a walk since the probe: re-read the marks (z indices stay valid)
                 stale = false;
 #pragma unroll
@@ -2035,9 +1736,7 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
             int hit = -1;
             int32_t zsel = 0, zfsel = 0;
             int64_t zpsel = -1;
-#if HYMET_BT_TRIV
             int32_t tqsel = 0, fqsel = 0;
-#endif
 #pragma unroll
             for (int c = kBtProbe - 1; c >= 0; c--) {  // the nearest unmarked entry at or below k wins
                 const uint64_t m = __ballot(tv[c] == 0 && 64 * c + lane >= d);
@@ -2047,10 +1746,8 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
                     zsel = __builtin_amdgcn_readlane(zc[c], h);
                     zfsel = __builtin_amdgcn_readlane(zfv[c], h);
                     zpsel = rlane64(zpv[c], h);
-#if HYMET_BT_TRIV
                     tqsel = __builtin_amdgcn_readlane(tqv[c], h);
                     fqsel = __builtin_amdgcn_readlane(fqv[c], h);
-#endif
                 }
             }
             hit = uni(hit);
@@ -2061,7 +1758,6 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
             const int64_t zi = (int64_t)uni(zsel);
             k = ptop - hit - 1;
             const int32_t zf = uni(zfsel);
-#if HYMET_BT_TRIV
             // a start whose predecessor was already used (or that has none) walks one node: its
             // score z.x - f[p] (or z.x) decides whether it stays used, and a one-anchor path is
             // never a chain (min_cnt >= 2).  No other mark changes, so the block stays fresh.
@@ -2071,7 +1767,6 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
                 c_walk++;
                 continue;
             }
-#endif
             stale = true;
             int64_t *buf = P.chain_ids + wpos;
             buf[0] = zi;  // every lane: same value, same address
@@ -2425,7 +2120,6 @@ __global__ __launch_bounds__(64) void chain_small_kernel(ChainParams P, const in
         F[i] = max_f, PJ[i] = max_j;
         P.f[g0 + i] = max_f;
         P.p[g0 + i] = max_j < 0 ? -1 : g0 + max_j;
-        if (HYMET_CHAIN_TZERO) P.t_global[g0 + i] = 0;
     }
 }
 
@@ -2467,8 +2161,7 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const in
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, kChainLds) != hipSuccess ||
         per_cu <= 0)
         per_cu = 8;
-    static const int waves_env = getenv("HYMET_CHAIN_WAVES") ? atoi(getenv("HYMET_CHAIN_WAVES")) : 0;  // A/B: resident waves per CU
-    if (waves_env > 0 && waves_env < per_cu) per_cu = waves_env;
+    per_cu = (int)env_int("HYMET_CHAIN_WAVES", per_cu, 1, per_cu);  // A/B: resident waves per CU
     const int64_t cap = (int64_t)ctx->n_cu * per_cu;
     if (blocks > cap) blocks = cap;
     // two profile scopes, one kernel each: the wave kernel (groups above kSmall anchors, the
@@ -2503,11 +2196,9 @@ int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, c
                      int min_cnt, int min_sc, int max_drop, int64_t *chain_ids, uint64_t *chain_u, int64_t *chain_first,
                      int32_t *n_chains, int64_t n_anchors) {
     if (n_groups <= 0) return HYMET_OK;
-    // t arrives zeroed (the chaining kernels clear it anchor by anchor, nonwork_fp_kernel the
-    // groups below min_cnt)
-    const char *ev = getenv("HYMET_BT_LONG");
-    const int64_t long_min = ev ? atoll(ev) : kBtLong;
-    const bool prof = getenv("HYMET_BT_PROF") != nullptr;
+    // t arrives zeroed (chain_set's fill; a chaining group that stamped it re-zeroed it)
+    const int64_t long_min = env_int("HYMET_BT_LONG", kBtLong, 0, INT64_MAX);
+    const bool prof = env_flag("HYMET_BT_PROF");
     DevBuf pbuf;
     if (prof) {
         HY_HIP(pbuf.alloc(64, ctx->stream));
@@ -2534,8 +2225,7 @@ int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, c
         // slower than 16 on C4 under the single work counter; with the striped counters 24 (the
         // register limit) measured faster than 16, one-stream (112 vs 116 ms/step) and
         // two-stream (1,585 vs 1,594 ms per bench step)
-        const char *ew = getenv("HYMET_BT_WAVES");
-        const int per_cu = ew ? std::max(1, atoi(ew)) : 24;
+        const int per_cu = (int)env_int("HYMET_BT_WAVES", 24, 1, 1024);
         const int64_t nb = std::min<int64_t>(n_work, (int64_t)ctx->n_cu * per_cu);
         hipLaunchKernelGGL(backtrack_long_kernel, dim3((unsigned)nb), dim3(64), 0, ctx->stream, P, order,
                            cnt.as<int32_t>(), cnt.as<int32_t>() + kBtCtrPad);

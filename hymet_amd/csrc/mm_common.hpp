@@ -34,10 +34,6 @@ __host__ __device__ __forceinline__ uint64_t hash64(uint64_t key) {
     return key;
 }
 
-// Device scratch from the library's caching allocator (hymet::scratch_alloc), returned to the
-// cache at scope exit.  The cache is per stream and all work of a context runs on its one
-// stream, so a block handed back while kernels that use it are still queued can be reissued
-// at once: the next user is queued behind them.
 // mm_est_err's get_mini_idx as a table lookup: per 64 query bases (each query's range padded
 // to a multiple of 64), a bit per base where a seeded minimizer starts and the query-relative
 // index of the word's first such minimizer; index(x) = base + popcount(bits below x).  16 B per
@@ -53,6 +49,10 @@ __device__ __forceinline__ int32_t mini_word_idx(const MiniWord &e, int32_t x) {
     return (e.bits >> (x & 63) & 1) ? (int32_t)(e.base + (uint32_t)__popcll(e.bits & below)) : -1;
 }
 
+// Device scratch from the library's caching allocator (hymet::scratch_alloc), returned to the
+// cache at scope exit.  The cache is per stream and all work of a context runs on its one
+// stream, so a block handed back while kernels that use it are still queued can be reissued
+// at once: the next user is queued behind them.
 struct DevBuf {
     void *p = nullptr;
     size_t n = 0, cls = 0;
@@ -113,7 +113,6 @@ int exclusive_scan_u32_i64(hymet_ctx *ctx, const uint32_t *in, int64_t *out, int
 // the same, asynchronous: `part` (scratch, kept alive by the caller) ends with the total at
 // index ceil(n / 4096)
 int scan_u32_i64(hymet_ctx *ctx, const uint32_t *in, int64_t *out, int64_t n, DevBuf &part, int64_t *mail = nullptr);
-// exclusive scan of n uint64 values (asynchronous; part ends with the total at ceil(n / 4096))
 // mailbox words (hymet_ctx::mbox_h) by use; each is read right after the sync that follows
 // the kernel storing it, so uses that never overlap may share a word
 enum : int { kMbScan = 0, kMbGmax = 1, kMbZBig = 2, kMbZBigTotal = 3, kMbFlag = 4, kMbRegBig = 5, kMbRegBig2 = 6, kMbQClass = 8,
@@ -146,6 +145,7 @@ inline int bits_for(int64_t v) {
 }
 // exclusive scan of uint32 counts into uint32 offsets (totals below 2^32)
 int scan_u32(hymet_ctx *ctx, const uint32_t *in, uint32_t *out, int64_t n, DevBuf &part, int64_t *mail = nullptr);
+// exclusive scan of n uint64 values (asynchronous; part ends with the total at ceil(n / 4096))
 int scan_u64(hymet_ctx *ctx, const uint64_t *in, uint64_t *out, int64_t n, DevBuf &part, int64_t *mail = nullptr);
 // inclusive running maximum of n int32 values (asynchronous)
 int inclusive_max_scan_i32(hymet_ctx *ctx, const int32_t *in, int32_t *out, int64_t n, DevBuf &part);
@@ -153,14 +153,6 @@ int inclusive_max_scan_i32(hymet_ctx *ctx, const int32_t *in, int32_t *out, int6
 // Per-query grouped sort of anchor keys (mm_asort.hip): key/val (n, query-major, query offsets
 // d_qoff[n_q + 1]) into the sorted anchor set okey (k1) / ax / ay (oval: scratch).  Returns 1
 // with nothing written where it does not apply (the caller's device sort then runs).
-// t (the backtrack's marks, zero before it runs) cleared by a fill of every anchor in chain_set
-// (0), or by the chaining kernels as each anchor is decided (1: the extra store per anchor made
-// the first-pass wave kernel ~3 % slower on the C4 dump, 6.65-6.81 vs 6.84-7.11 ms, while the
-// fill overlaps the other mapping stream's kernels; profiles/r06_tzero/)
-#ifndef HYMET_CHAIN_TZERO
-#define HYMET_CHAIN_TZERO 0
-#endif
-
 // hb: the set's group-head bitmap (head_bits_bytes(n); AnchorOut::head); ax32: x's low words.
 // d_stats (nullable, four zeroed counters): what the block sorts did -- segments and anchors
 // finished by their outlier path, segments and anchors that took the full sort.

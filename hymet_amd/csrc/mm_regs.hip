@@ -58,16 +58,6 @@ __device__ void heap_sort(T *a, int64_t n, Less less) {
     }
 }
 
-__device__ __forceinline__ int64_t upper_idx(const int64_t *off, int64_t n, int64_t v) {  // last s with off[s] <= v
-    int64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= v) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 struct RegParams {
     const uint64_t *ax, *ay;       // the chained anchor set
     const int64_t *ids, *cfirst;   // backtrack output (chains end -> start) and each chain's first slot in it
@@ -1203,13 +1193,11 @@ int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const
     // HYMET_REG_LDS (chains up to which the wave kernel works in LDS; 32: every wave query on the
     // global-scratch path from 33 chains: a query's share of that scratch, 2n entries, holds
     // its power-of-two working size only from there)
-    const char *ew = getenv("HYMET_REG_WAVE"), *el = getenv("HYMET_REG_LDS");
-    if (ew && atoi(ew) >= 0) P.wave_min = atoi(ew);
-    if (el) P.lds_max = std::max(32, std::min(kRegSmall, atoi(el)));
-    if (const char *ep = getenv("HYMET_REG_PRIM")) P.prim_regs = std::max(0, std::min(64, atoi(ep)));
+    P.wave_min = (int)env_int("HYMET_REG_WAVE", P.wave_min, 0, INT32_MAX);
+    P.lds_max = (int)env_int("HYMET_REG_LDS", P.lds_max, 32, kRegSmall);
+    P.prim_regs = (int)env_int("HYMET_REG_PRIM", P.prim_regs, 0, 64);
     ProfScope _ps(ctx, "mm_regions", (double)NC * (8.0 + 8.0 + 4.0 * 5) + (double)n_q * 64.0);  // chain + stats reads, reg writes
-    static const bool reg_stats = getenv("HYMET_REG_STATS") != nullptr;  // diagnostic: chains per query
-    if (reg_stats) {
+    if (env_flag("HYMET_REG_STATS")) {  // diagnostic: chains per query
         std::vector<int64_t> hq(n_q + 1);
         HY_HIP(hipMemcpyAsync(hq.data(), qc, 8 * (size_t)(n_q + 1), hipMemcpyDeviceToHost, st));
         HY_HIP(hipStreamSynchronize(st));
@@ -1224,7 +1212,7 @@ int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const
                 n_q, (long long)NB, (long long)tot, (long long)mx, (long long)h[0], (long long)h[1], (long long)h[2], (long long)h[3],
                 (long long)h[4], (long long)h[5], (long long)big_tot);
     }
-    if (getenv("HYMET_REG_PROF")) {
+    if (env_flag("HYMET_REG_PROF")) {
         HY_HIP(hipMalloc((void **)&P.prof, 8 * 8));
         HY_HIP(hipMemsetAsync(P.prof, 0, 8 * 8, st));
     }

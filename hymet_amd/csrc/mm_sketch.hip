@@ -235,7 +235,7 @@ int sketch_sequences(hymet_ctx *ctx, const uint32_t *d_2b, const uint32_t *d_mas
     // in practice, and an overflow falls back to the two passes.
     constexpr int kSlotCap = kChunk + 64;
     bool done = false;
-    if (n_chunks > 0 && (double)n_chunks * kSlotCap * 16.0 <= 2.0e9 && !getenv("HYMET_SKETCH_TWO_PASS")) {
+    if (n_chunks > 0 && (double)n_chunks * kSlotCap * 16.0 <= 2.0e9 && !env_flag("HYMET_SKETCH_TWO_PASS")) {
         DevBuf sx, sy;
         HY_HIP(sx.alloc(8 * (size_t)n_chunks * kSlotCap, ctx->stream));
         HY_HIP(sy.alloc(8 * (size_t)n_chunks * kSlotCap, ctx->stream));

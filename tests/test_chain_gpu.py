@@ -69,6 +69,25 @@ def test_chain_dense_repeats(gpu):
     check(gpu, x, y, cap=20000)
 
 
+def tile_boundary_set():
+    """16,584 anchors whose groups (one target each) start on both sides of a head-bitmap word
+    (64) and of a grouping tile (16,384), with one- and two-anchor groups in the middle and a
+    last group of one anchor."""
+    rng = np.random.default_rng(6)
+    sizes = [63, 1, 1, 4935, 1, 2, 11380, 1, 1, 198, 1]
+    parts = [colinear(rng, m, rid=r, t0=int(rng.integers(0, 10**6)), spurious=0.0) for r, m in enumerate(sizes)]
+    return assemble(parts)
+
+
+def test_chain_group_heads_at_tile_boundaries(gpu):
+    x, y = tile_boundary_set()
+    n = len(x)
+    assert n == 16384 + 200
+    heads = np.flatnonzero(np.r_[True, (x[1:] >> np.uint64(32)) != (x[:-1] >> np.uint64(32))])
+    assert heads.tolist() == [0, 63, 64, 65, 5000, 5001, 5003, 16383, 16384, 16385, n - 1]
+    check(gpu, x, y)
+
+
 def test_chain_grid_ties(gpu):
     rng = np.random.default_rng(4)
     parts = []
