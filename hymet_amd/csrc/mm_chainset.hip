@@ -14,12 +14,12 @@ namespace hymet {
 namespace mm {
 
 int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const int64_t *g_start, const uint8_t *g_qfirst,
-                 const int32_t *order, int32_t n_work, int32_t *f, int64_t *p, int32_t *t_global, int max_dist,
+                 const int32_t *order, int32_t n_work, int32_t *f, int32_t *p, int32_t *t_global, int max_dist,
                  int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap, float pen_skip,
                  int64_t n_anchors, int64_t n_groups);
-int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int64_t *p, int32_t *t,
+int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int32_t *p, int32_t *t,
                      const int32_t *z_cnt, const int32_t *z_idx, int32_t n_groups, const int32_t *order, int32_t n_work,
-                     int min_cnt, int min_sc, int max_drop, int64_t *chain_ids, uint64_t *chain_u, int64_t *chain_first,
+                     int min_cnt, int min_sc, int max_drop, int32_t *chain_ids, uint64_t *chain_u, int64_t *chain_first,
                      int32_t *n_chains, int64_t n_anchors);
 
 namespace {
@@ -138,7 +138,7 @@ __global__ void max_group_kernel(const int64_t *g_start, const int32_t *order, i
 
 // groups of fewer than min_cnt anchors: f = 0, p = -1, t = 0 (the chaining kernels write f and
 // p of the anchors of every work group, so neither needs a pass over the set)
-__global__ void nonwork_fp_kernel(const int64_t *g_start, int32_t G, int min_cnt, int32_t *f, int64_t *p, int32_t *t) {
+__global__ void nonwork_fp_kernel(const int64_t *g_start, int32_t G, int min_cnt, int32_t *f, int32_t *p, int32_t *t) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
     const int64_t a0 = g_start[g], a1 = g_start[g + 1];
@@ -537,7 +537,7 @@ __global__ void zbig_scatter_kernel(ZParams P, const uint32_t *sval) {
 
 // chain list entries: (key = first anchor index) -> sorted
 __global__ void chain_list_kernel(const int64_t *g_start, const int32_t *n_chains, const int64_t *c_pos, int32_t G,
-                                  const uint64_t *chain_u, const int64_t *chain_first, const int64_t *chain_ids,
+                                  const uint64_t *chain_u, const int64_t *chain_first, const int32_t *chain_ids,
                                   uint64_t *ckey, uint64_t *cu, int64_t *cfirst) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
@@ -566,7 +566,7 @@ __global__ void chain_cnt_kernel(const uint64_t *cu, const uint32_t *cq, const u
 // long join, first pass (map.c's rmq rescue): a query is re-chained when it has more than one
 // chain and its first chain (compact order) leaves too much of it uncovered -- read from the
 // chain list before the copy
-__global__ void rechain_flag_kernel(const uint64_t *ay, const int64_t *chain_ids, const uint64_t *cu, const int64_t *cfirst,
+__global__ void rechain_flag_kernel(const uint64_t *ay, const int32_t *chain_ids, const uint64_t *cu, const int64_t *cfirst,
                                     const int64_t *qc, const int64_t *qlen, int n_q, int rescue_size, float rescue_ratio,
                                     uint32_t *flag) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -594,7 +594,7 @@ __global__ void chain_qb_kernel(const int64_t *qc, const int64_t *bpos, int64_t 
 // anchors of chain c in start -> end order, and c per anchor (the chains of queries the long
 // join re-chains have no anchors here: cnt 0)
 __global__ __launch_bounds__(256) void chain_copy_kernel(const uint64_t *cu, const int64_t *cfirst, const int64_t *bpos,
-                                                         const int64_t *chain_ids, const uint64_t *ax, const uint64_t *ay,
+                                                         const int32_t *chain_ids, const uint64_t *ax, const uint64_t *ay,
                                                          int64_t n_chain, int64_t nb, uint64_t *bx, uint64_t *by,
                                                          int32_t *bchain) {
     // flat over the output anchors (~48 B each, bandwidth-bound: C4 copies ~236 M per batch at
@@ -908,11 +908,11 @@ static int build_work_list(hymet_ctx *ctx, const Groups &Gr, int min_cnt, WorkLi
 static int chain_dp(hymet_ctx *ctx, const DpArgs &a, const AnchorSet &A, const Groups &Gr, const WorkList &W, DevBuf &f,
                     DevBuf &p, DevBuf &t) {
     HY_HIP(f.alloc(4 * (size_t)A.n, ctx->stream));
-    HY_HIP(p.alloc(8 * (size_t)A.n, ctx->stream));
-    LAUNCH1(nonwork_fp_kernel, Gr.G, Gr.g_start.as<int64_t>(), (int32_t)Gr.G, a.min_cnt, f.as<int32_t>(), p.as<int64_t>(),
+    HY_HIP(p.alloc(4 * (size_t)A.n, ctx->stream));
+    LAUNCH1(nonwork_fp_kernel, Gr.G, Gr.g_start.as<int64_t>(), (int32_t)Gr.G, a.min_cnt, f.as<int32_t>(), p.as<int32_t>(),
             t.as<int32_t>());
     return launch_chain(ctx, A.ax32.as<int32_t>(), A.ay.as<uint64_t>(), Gr.g_start.as<int64_t>(), Gr.qfirst.as<uint8_t>(),
-                        W.order.as<int32_t>(), (int32_t)W.n_work, f.as<int32_t>(), p.as<int64_t>(), t.as<int32_t>(), a.max_dist,
+                        W.order.as<int32_t>(), (int32_t)W.n_work, f.as<int32_t>(), p.as<int32_t>(), t.as<int32_t>(), a.max_dist,
                         a.max_dist_inner, a.bw, a.max_chn_skip, a.cap_rmq_size, a.pen_gap, a.pen_skip, A.n, Gr.G);
 }
 
@@ -983,13 +983,13 @@ static int z_order(hymet_ctx *ctx, int min_sc, const DevBuf &f, int64_t n, const
 
 static int backtrack(hymet_ctx *ctx, const hymet_mm_opt *opt, int bw, int64_t n, const Groups &Gr, const WorkList &W,
                      const DevBuf &f, const DevBuf &p, DevBuf &t, const ZOrder &Z, Backtrack &B) {
-    HY_HIP(B.ids.alloc(8 * (size_t)n, ctx->stream));
+    HY_HIP(B.ids.alloc(4 * (size_t)n, ctx->stream));
     HY_HIP(B.u.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(B.first.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(B.n_chains.alloc(4 * (size_t)Gr.G, ctx->stream));
-    return launch_backtrack(ctx, Gr.g_start.as<int64_t>(), f.as<int32_t>(), p.as<int64_t>(), t.as<int32_t>(), Z.cnt.as<int32_t>(),
+    return launch_backtrack(ctx, Gr.g_start.as<int64_t>(), f.as<int32_t>(), p.as<int32_t>(), t.as<int32_t>(), Z.cnt.as<int32_t>(),
                             Z.idx.as<int32_t>(), (int32_t)Gr.G, W.order.as<int32_t>(), (int32_t)W.n_work, opt->min_cnt,
-                            opt->min_chain_score, bw, B.ids.as<int64_t>(), B.u.as<uint64_t>(), B.first.as<int64_t>(),
+                            opt->min_chain_score, bw, B.ids.as<int32_t>(), B.u.as<uint64_t>(), B.first.as<int64_t>(),
                             B.n_chains.as<int32_t>(), n);
 }
 
@@ -1008,7 +1008,7 @@ static int chain_list(hymet_ctx *ctx, const AnchorSet &A, int n_q, const Groups 
     HY_HIP(cu.alloc(8 * (size_t)(NC + 1), ctx->stream));
     HY_HIP(cf.alloc(8 * (size_t)(NC + 1), ctx->stream));
     LAUNCH1(chain_list_kernel, G, Gr.g_start.as<int64_t>(), B.n_chains.as<int32_t>(), cpos.as<int64_t>(), (int32_t)G,
-            B.u.as<uint64_t>(), B.first.as<int64_t>(), B.ids.as<int64_t>(), ckey.as<uint64_t>(), cu.as<uint64_t>(),
+            B.u.as<uint64_t>(), B.first.as<int64_t>(), B.ids.as<int32_t>(), ckey.as<uint64_t>(), cu.as<uint64_t>(),
             cf.as<int64_t>());
     // sort chains by first anchor: pairs (key, perm) then gather
     DevBuf perm, perm2, ckeyb;
@@ -1045,7 +1045,7 @@ static int chain_layout(hymet_ctx *ctx, const AnchorSet &A, int n_q, const DevBu
     const uint32_t *qflag = nullptr;
     if (lj) {
         HY_HIP(lj->flag.alloc(4 * (size_t)n_q, ctx->stream));
-        LAUNCH1(rechain_flag_kernel, n_q, A.ay.as<uint64_t>(), chain_ids.as<int64_t>(), C.cu.as<uint64_t>(),
+        LAUNCH1(rechain_flag_kernel, n_q, A.ay.as<uint64_t>(), chain_ids.as<int32_t>(), C.cu.as<uint64_t>(),
                 cfirst.as<int64_t>(), C.d_qc.as<int64_t>(), lj->qlen, n_q, lj->rescue_size, lj->rescue_ratio,
                 lj->flag.as<uint32_t>());
         if (lj->mark_only) qflag = lj->flag.as<uint32_t>();
@@ -1066,7 +1066,7 @@ static int chain_layout(hymet_ctx *ctx, const AnchorSet &A, int n_q, const DevBu
         HY_HIP(C.bchain.alloc(4 * (size_t)(NB + 1), ctx->stream));
         if (NC > 0 && NB > 0)
             LAUNCH1(chain_copy_kernel, NB, C.cu.as<uint64_t>(), cfirst.as<int64_t>(), C.cboff.as<int64_t>(),
-                    chain_ids.as<int64_t>(), A.ax.as<uint64_t>(), A.ay.as<uint64_t>(), NC, NB, C.bx.as<uint64_t>(),
+                    chain_ids.as<int32_t>(), A.ax.as<uint64_t>(), A.ay.as<uint64_t>(), NC, NB, C.bx.as<uint64_t>(),
                     C.by.as<uint64_t>(), C.bchain.as<int32_t>());
     }
     HY_HIP(C.d_qb.alloc(8 * (size_t)(n_q + 1), ctx->stream));
@@ -1089,6 +1089,7 @@ static int chain_layout(hymet_ctx *ctx, const AnchorSet &A, int n_q, const DevBu
 int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_skip, int bw, AnchorSet &A, int n_q,
               ChainSet &C, LeanJoin *lj, bool copy) {
     const int64_t n = A.n;
+    HY_ARG(n >= 0 && n < INT32_MAX, "chain_set: an anchor set of 2^31 anchors or more (32-bit chain links)");
     C.ax = A.ax.as<uint64_t>(), C.ay = A.ay.as<uint64_t>();
     if (n == 0) {
         HY_HIP(C.d_qc.alloc(8 * (size_t)(n_q + 1), ctx->stream));
@@ -1203,7 +1204,9 @@ extern "C" int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint
     rc = chain_dp(ctx, DpArgs{max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, pen_gap, pen_skip, 1}, A, Gr, W, f, p, t);
     if (rc) return rc;
     HY_HIP(hipMemcpyAsync(h_f, f.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    HY_HIP(hipMemcpyAsync(h_p, p.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> p32((size_t)n);  // the links are 32-bit on the device: widened for the caller
+    HY_HIP(hipMemcpyAsync(p32.data(), p.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HY_HIP(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n; i++) h_p[i] = p32[(size_t)i];
     return HYMET_OK;
 }

@@ -150,15 +150,25 @@ int scan_u64(hymet_ctx *ctx, const uint64_t *in, uint64_t *out, int64_t n, DevBu
 // inclusive running maximum of n int32 values (asynchronous)
 int inclusive_max_scan_i32(hymet_ctx *ctx, const int32_t *in, int32_t *out, int64_t n, DevBuf &part);
 
-// Per-query grouped sort of anchor keys (mm_asort.hip): key/val (n, query-major, query offsets
-// d_qoff[n_q + 1]) into the sorted anchor set okey (k1) / ax / ay (oval: scratch).  Returns 1
-// with nothing written where it does not apply (the caller's device sort then runs).
+// An anchor on its way to the grouped sort is one word, W = (rev << (rb + pb) | rid << pb | rpos)
+// << ybits | y: its order inside a query (the query comes from the offsets, the span in y's
+// high word is the batch's constant).  -> ybits for queries up to max_qlen, or 0 where the
+// word would pass 63 bits (all-ones is the sorts' padding) and the key / value pair with the
+// device sort is used instead.
+inline int anchor_word_ybits(int rb, int pb, int64_t max_qlen) {
+    int yb = 1;
+    while (yb <= 32 && (1ll << yb) <= max_qlen) yb++;
+    return yb <= 32 && 1 + rb + pb + yb <= 63 ? yb : 0;
+}
+// Per-query grouped sort of anchor words (mm_asort.hip): word (n, query-major, query offsets
+// d_qoff[n_q + 1]) into the sorted anchor set ax / ay (oword: scratch).  Returns 1 with
+// nothing written where it does not apply (no anchors, or no word for the layout).
 // hb: the set's group-head bitmap (head_bits_bytes(n); AnchorOut::head); ax32: x's low words.
 // d_stats (nullable, four zeroed counters): what the block sorts did -- segments and anchors
 // finished by their outlier path, segments and anchors that took the full sort.
-int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, const uint32_t *val, int64_t n, const int64_t *d_qoff, int n_q,
-                        int rb, int pb, uint64_t yhi, int64_t max_qlen, uint64_t *okey, uint32_t *oval, uint64_t *ax,
-                        uint64_t *ay, uint32_t *hb, uint32_t *ax32, unsigned long long *d_stats = nullptr);
+int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *word, int64_t n, const int64_t *d_qoff, int n_q, int rb, int pb,
+                        uint64_t yhi, int64_t max_qlen, uint64_t *oword, uint64_t *ax, uint64_t *ay, uint32_t *hb,
+                        uint32_t *ax32, unsigned long long *d_stats = nullptr);
 // bytes of an anchor set's group-head bitmap: one bit per anchor, in whole 64-bit words (the
 // group kernels read two words per thread)
 inline size_t head_bits_bytes(int64_t n) { return 8 * (size_t)((n + 63) / 64 + 1); }

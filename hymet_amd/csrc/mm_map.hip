@@ -38,7 +38,7 @@ struct hymet_mm_result {
 namespace hymet {
 namespace mm {
 
-int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const int64_t *ids, const int64_t *cfirst,
+int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const int32_t *ids, const int64_t *cfirst,
                    const uint64_t *cu, const int64_t *cboff,
                    const int64_t *qc, const int64_t *qb, const uint64_t *mini_pos, const int64_t *mp_off, const int64_t *qlen,
                    const uint32_t *name_hash, const int32_t *rep_len, const int64_t *ref_len, int n_q, const hymet_mm_opt *o,
@@ -366,10 +366,13 @@ __global__ void write_anchors_kernel(AnchorParams P) {
     }
 }
 
-// Anchor keys (the default path): one 64-bit key per anchor packing exactly the sort order
-// of (query, x) -- K = q | rev | rid | rpos, field widths from the batch (query count,
-// index sequences, longest index sequence) -- and the low 32 bits of y as the value.  The
-// high bits of y hold the span, which is k for every minimizer of a non-HPC sketch.  One
+// Anchor keys (the default path): one 64-bit word per anchor packing exactly its sort order
+// inside its query -- W = (rev | rid | rpos) << ybits | y's low word, field widths from the
+// batch (index sequences, longest index sequence, longest query; anchor_word_ybits) -- for
+// the grouped sort, which takes the query from the anchor offsets.  Where that sort is off
+// or the word does not fit (ybits == 0): the key K = q | rev | rid | rpos, exactly the sort
+// order of (query, x), and the low 32 bits of y as a value of its own, for the device sort.
+// The high bits of y hold the span, which is k for every minimizer of a non-HPC sketch.  One
 // block per 256 consecutive minimizers: the block stages their anchor offsets, position-list
 // starts and query coordinates in LDS, then its 256 lanes sweep the block's anchors
 // (contiguous in both the position lists and the output), finding each anchor's minimizer
@@ -385,6 +388,7 @@ struct AnchorKeyParams {
     const uint64_t *ipos;
     int64_t n;                // minimizers
     int rb, pb;               // bits for rid / rpos
+    int ybits;                // > 0: words (no val)
     uint64_t *key;
     uint32_t *val;
     const int64_t *mp_pos;
@@ -428,8 +432,14 @@ __global__ __launch_bounds__(256) void write_anchor_keys_kernel(AnchorKeyParams 
         const uint32_t rpos = (uint32_t)rk >> 1;
         const uint64_t rid = rk >> 32;
         const uint32_t rev = ((uint32_t)rk & 1) != s_strand[lo];
-        P.key[a] = s_q[lo] | (uint64_t)rev << sh_rev | rid << P.pb | rpos;
-        P.val[a] = rev ? s_yr[lo] : s_yf[lo];
+        const uint64_t k = (uint64_t)rev << sh_rev | rid << P.pb | rpos;
+        const uint32_t y = rev ? s_yr[lo] : s_yf[lo];
+        if (P.ybits) {
+            P.key[a] = k << P.ybits | y;
+        } else {
+            P.key[a] = s_q[lo] | k;
+            P.val[a] = y;
+        }
     }
 }
 
@@ -517,7 +527,7 @@ __global__ void rechain_gather_kernel(const uint64_t *bx, const uint64_t *by, co
 // the tail); the block's first query by one binary search, each lane's by a short forward walk
 __global__ __launch_bounds__(256) void rechain_keys_kernel(const uint64_t *bx, const uint64_t *by, const int64_t *qb,
                                                            const int64_t *new_off, int n_q, int64_t n, int rb, int pb,
-                                                           uint64_t *key, uint32_t *val) {
+                                                           int ybits, uint64_t *key, uint32_t *val) {
     __shared__ int s_q0;
     const int64_t a0 = (int64_t)blockIdx.x * blockDim.x;
     if (threadIdx.x == 0) s_q0 = upper_idx(new_off, n_q, a0);
@@ -528,8 +538,13 @@ __global__ __launch_bounds__(256) void rechain_keys_kernel(const uint64_t *bx, c
     while (q + 1 < n_q && new_off[q + 1] <= a) q++;  // last q with new_off[q] <= a
     const int64_t i = qb[q] + (a - new_off[q]);
     const uint64_t ax = bx[i];
-    key[a] = (uint64_t)q << (1 + rb + pb) | (ax >> 63) << (rb + pb) | (ax << 1 >> 33) << pb | (uint32_t)ax;
-    val[a] = (uint32_t)by[i];
+    const uint64_t k = (ax >> 63) << (rb + pb) | (ax << 1 >> 33) << pb | (uint32_t)ax;
+    if (ybits) {  // words, as write_anchor_keys_kernel's
+        key[a] = k << ybits | (uint32_t)by[i];
+    } else {
+        key[a] = (uint64_t)q << (1 + rb + pb) | k;
+        val[a] = (uint32_t)by[i];
+    }
 }
 
 // per query: regions kept (first-pass chains, or the long-join re-chain's for flagged queries)
@@ -621,11 +636,48 @@ static int sort_anchor_set(hymet_ctx *ctx, DevBuf &x, DevBuf &y, DevBuf &k1, Dev
     return HYMET_OK;
 }
 
-// sort anchor keys (write_anchor_keys_kernel / rechain_keys_kernel) into an AnchorSet: the
-// per-query grouped sort (mm_asort.hip), or one LSD radix sort over the key's significant
-// bits where that does not apply (HYMET_ANCHOR_GSORT=0 forces it), then unpack to (x, y)
+// sort anchor words (write_anchor_keys_kernel / rechain_keys_kernel with ybits > 0) into an
+// AnchorSet: the per-query grouped sort (mm_asort.hip), which writes (x, y) itself
+static int sort_anchor_words(hymet_ctx *ctx, DevBuf &word, int64_t n, int rb, int pb, int yhi, const int64_t *d_qoff, int n_q,
+                             int64_t max_qlen, AnchorSet &out) {
+    DevBuf wb;
+    HY_HIP(wb.alloc(8 * (size_t)n, ctx->stream));
+    HY_HIP(out.ax.alloc(8 * (size_t)n, ctx->stream));
+    HY_HIP(out.ay.alloc(8 * (size_t)n, ctx->stream));
+    HY_HIP(out.hb.alloc(head_bits_bytes(n), ctx->stream));
+    HY_HIP(out.ax32.alloc(4 * (size_t)n, ctx->stream));
+    out.n = n;
+    // HYMET_ASORT_STATS=1: every batch's block-sort counts on stderr (a measuring aid: it
+    // adds a stream synchronise per batch) -- segments and anchors finished by the outlier
+    // path, segments and anchors that took the full sort
+    const bool log_stats = env_flag("HYMET_ASORT_STATS");
+    DevBuf sstat;
+    if (log_stats) {
+        HY_HIP(sstat.alloc(32, ctx->stream));
+        HY_HIP(hipMemsetAsync(sstat.p, 0, 32, ctx->stream));
+    }
+    const int rc = grouped_anchor_sort(ctx, word.as<uint64_t>(), n, d_qoff, n_q, rb, pb, (uint64_t)yhi, max_qlen,
+                                       wb.as<uint64_t>(), out.ax.as<uint64_t>(), out.ay.as<uint64_t>(),
+                                       out.hb.as<uint32_t>(), out.ax32.as<uint32_t>(),
+                                       log_stats ? sstat.as<unsigned long long>() : nullptr);
+    if (rc == 1) return hymet::fail(HYMET_E_INTERNAL, "sort_anchor_words: anchor words emitted for a layout without one");
+    if (rc) return rc;
+    if (log_stats) {
+        unsigned long long h[4] = {};
+        HY_HIP(hipMemcpyAsync(h, sstat.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+        HY_HIP(hipStreamSynchronize(ctx->stream));
+        fprintf(stderr, "[asort] anchors %lld fast_segs %llu fast_anchors %llu full_segs %llu full_anchors %llu\n",
+                (long long)n, h[0], h[1], h[2], h[3]);
+    }
+    out.has_hb = out.has_x32 = true;
+    return HYMET_OK;
+}
+
+// sort anchor keys (write_anchor_keys_kernel / rechain_keys_kernel with ybits == 0: the
+// grouped sort is off, HYMET_ANCHOR_GSORT=0, or has no word for the layout) into an AnchorSet:
+// one LSD radix sort over the key's significant bits, then unpack to (x, y)
 static int sort_anchor_keys(hymet_ctx *ctx, DevBuf &key, DevBuf &val, int64_t n, int end_bit, int rb, int pb, int yhi,
-                            const int64_t *d_qoff, int n_q, int64_t max_qlen, AnchorSet &out) {
+                            AnchorSet &out) {
     DevBuf kb, vb;
     HY_HIP(kb.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(vb.alloc(4 * (size_t)n, ctx->stream));
@@ -634,34 +686,6 @@ static int sort_anchor_keys(hymet_ctx *ctx, DevBuf &key, DevBuf &val, int64_t n,
     out.n = n;
     uint64_t *kk = key.as<uint64_t>(), *kka = kb.as<uint64_t>();
     uint32_t *vv = val.as<uint32_t>(), *vva = vb.as<uint32_t>();
-    if (env_flag("HYMET_ANCHOR_GSORT", true)) {
-        HY_HIP(out.hb.alloc(head_bits_bytes(n), ctx->stream));
-        HY_HIP(out.ax32.alloc(4 * (size_t)n, ctx->stream));
-        // HYMET_ASORT_STATS=1: every batch's block-sort counts on stderr (a measuring aid: it
-        // adds a stream synchronise per batch) -- segments and anchors finished by the outlier
-        // path, segments and anchors that took the full sort
-        const bool log_stats = env_flag("HYMET_ASORT_STATS");
-        DevBuf sstat;
-        if (log_stats) {
-            HY_HIP(sstat.alloc(32, ctx->stream));
-            HY_HIP(hipMemsetAsync(sstat.p, 0, 32, ctx->stream));
-        }
-        const int rc = grouped_anchor_sort(ctx, kk, vv, n, d_qoff, n_q, rb, pb, (uint64_t)yhi, max_qlen, kka, vva,
-                                           out.ax.as<uint64_t>(), out.ay.as<uint64_t>(), out.hb.as<uint32_t>(),
-                                           out.ax32.as<uint32_t>(), log_stats ? sstat.as<unsigned long long>() : nullptr);
-        if (log_stats && rc == HYMET_OK) {
-            unsigned long long h[4] = {};
-            HY_HIP(hipMemcpyAsync(h, sstat.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-            HY_HIP(hipStreamSynchronize(ctx->stream));
-            fprintf(stderr, "[asort] anchors %lld fast_segs %llu fast_anchors %llu full_segs %llu full_anchors %llu\n",
-                    (long long)n, h[0], h[1], h[2], h[3]);
-        }
-        if (rc == HYMET_OK) {
-            out.has_hb = out.has_x32 = true;
-            return HYMET_OK;
-        }
-        if (rc != 1) return rc;
-    }
     int rc = sort_pairs<uint64_t, uint32_t>(ctx, kk, kka, vv, vva, n, 0, end_bit, "radix_sort_anchors");
     if (rc) return rc;
     {
@@ -765,6 +789,7 @@ struct MapBatch {
     // whether (query, strand, rid, rpos) fits one 64-bit key
     int rb = 0, pb = 0, key1_bits = 0;
     bool key_path = false;
+    int ybits = 0;  // > 0: the key path emits anchor words for the grouped sort (anchor_word_ybits)
 };
 
 // 1 sketch: the queries' minimizers, lengths and name hashes on the device
@@ -951,6 +976,7 @@ static int first_pass_anchors(MapBatch &B, AnchorSet &S1) {
     int64_t A = 0;
     int rc = scan_flags(ctx, seed_n.as<uint32_t>(), M, a_pos, &A);
     if (rc) return rc;
+    HY_ARG(A <= anchor_cap(), "hymet_mm_map: the batch has more anchors than 32-bit chain links hold (map fewer bases per batch)");
     HY_HIP(mflag.alloc(4 * (size_t)(M + 1), st));
     LAUNCH1(nz_flag_kernel, M, seed_n.as<uint32_t>(), M, mflag.as<uint32_t>());
     rc = scan_flags(ctx, mflag.as<uint32_t>(), M, mp_pos, &B.NM);
@@ -977,22 +1003,28 @@ static int first_pass_anchors(MapBatch &B, AnchorSet &S1) {
     // one-key anchor sort when (query, strand, rid, rpos) fits 64 bits (always, short of
     // ~2^20 queries per batch against chromosome-scale targets); else the two-key path
     B.key_path = B.key1_bits + B.pb <= 64 && !env_flag("HYMET_ANCHOR_LEGACY");
+    // anchors as words for the grouped sort where it is on and has a word for this batch's layout
+    B.ybits = B.key_path && env_flag("HYMET_ANCHOR_GSORT", true) ? anchor_word_ybits(B.rb, B.pb, B.max_qlen) : 0;
     if (B.key_path) {
+        const bool words = B.ybits > 0 && A > 0;
         DevBuf key, val;
         HY_HIP(key.alloc(8 * (size_t)(A + 1), st));
-        HY_HIP(val.alloc(4 * (size_t)(A + 1), st));
+        if (!words) HY_HIP(val.alloc(4 * (size_t)(A + 1), st));
         AnchorKeyParams P{mx.as<uint64_t>(), my.as<uint64_t>(), seed_n.as<uint32_t>(), a_pos.as<int64_t>(),
                           qid.as<uint32_t>(), d_qlen.as<int64_t>(), idx->d_koff, idx->d_pos, M, B.rb, B.pb,
-                          key.as<uint64_t>(), val.as<uint32_t>(), mp_pos.as<int64_t>(), B.mini_pos.as<uint64_t>()};
+                          words ? B.ybits : 0, key.as<uint64_t>(), val.as<uint32_t>(), mp_pos.as<int64_t>(),
+                          B.mini_pos.as<uint64_t>()};
         {
-            ProfScope _ps(ctx, "mm_anchors", (double)A * (8.0 + 12.0));  // position fetch + key/value write
+            // position fetch + key/value write; the benchmark counts anchors as this scope's bytes
+            // / 20, so the constant stays though a word is 8 B where a key and its value were 12
+            ProfScope _ps(ctx, "mm_anchors", (double)A * (8.0 + 12.0));
             if (M > 0) {
                 hipLaunchKernelGGL(write_anchor_keys_kernel, dim3((unsigned)cdiv(M, 256)), dim3(256), 0, st, P);
                 HY_CHECK_LAUNCH("write_anchor_keys_kernel");
             }
         }
-        return sort_anchor_keys(ctx, key, val, A, B.key1_bits + B.pb, B.rb, B.pb, idx->k, S1.d_off.as<int64_t>(), n_q,
-                                B.max_qlen, S1);
+        if (words) return sort_anchor_words(ctx, key, A, B.rb, B.pb, idx->k, S1.d_off.as<int64_t>(), n_q, B.max_qlen, S1);
+        return sort_anchor_keys(ctx, key, val, A, B.key1_bits + B.pb, B.rb, B.pb, idx->k, S1);
     }
     DevBuf x, y, k1, k2, val;
     HY_HIP(x.alloc(8 * (size_t)(A + 1), st));
@@ -1027,18 +1059,20 @@ static int long_join_anchors(MapBatch &B, const AnchorSet &S1, const ChainSet &C
     if (rc) return rc;
     any = mb_read(ctx, kMbFlag) != 0;
     if (!any) return HYMET_OK;
+    HY_ARG(A2 <= anchor_cap(), "hymet_mm_map: the long join has more anchors than 32-bit chain links hold");
     if (lj.mark_only) {
         // the flagged queries' chain anchors (t == 2 from the backtrack), compacted out of
         // the first-pass set in its (key, y) order -- already the long join's sorted set
         rc = marked_anchor_set(ctx, S1, lj, flag.as<uint32_t>(), n_q, A2, S2);
     } else if (B.key_path) {
+        const bool words = B.ybits > 0 && A2 > 0;
         DevBuf key, val;
         HY_HIP(key.alloc(8 * (size_t)(A2 + 1), st));
-        HY_HIP(val.alloc(4 * (size_t)(A2 + 1), st));
+        if (!words) HY_HIP(val.alloc(4 * (size_t)(A2 + 1), st));
         LAUNCH1(rechain_keys_kernel, A2, C1.bx.as<uint64_t>(), C1.by.as<uint64_t>(), C1.d_qb.as<int64_t>(),
-                S2.d_off.as<int64_t>(), n_q, A2, B.rb, B.pb, key.as<uint64_t>(), val.as<uint32_t>());
-        rc = sort_anchor_keys(ctx, key, val, A2, B.key1_bits + B.pb, B.rb, B.pb, B.idx->k, S2.d_off.as<int64_t>(), n_q,
-                              B.max_qlen, S2);
+                S2.d_off.as<int64_t>(), n_q, A2, B.rb, B.pb, words ? B.ybits : 0, key.as<uint64_t>(), val.as<uint32_t>());
+        rc = words ? sort_anchor_words(ctx, key, A2, B.rb, B.pb, B.idx->k, S2.d_off.as<int64_t>(), n_q, B.max_qlen, S2)
+                   : sort_anchor_keys(ctx, key, val, A2, B.key1_bits + B.pb, B.rb, B.pb, B.idx->k, S2);
     } else {
         DevBuf x, y, k1, k2, val;
         HY_HIP(x.alloc(8 * (size_t)(A2 + 1), st));
@@ -1069,7 +1103,7 @@ static int run_regions(MapBatch &B, ChainSet &C, DevBuf &rg, DevBuf &nr, const u
     HY_HIP(cov.alloc(8 * (size_t)(NC + 1), st));
     HY_HIP(tmp.alloc(4 * (size_t)(NC + 1), st));
     HY_HIP(nr.alloc(4 * (size_t)B.n_q, st));
-    return launch_regions(B.ctx, C.ax, C.ay, C.ids.as<int64_t>(), C.cfirst.as<int64_t>(), C.cu.as<uint64_t>(),
+    return launch_regions(B.ctx, C.ax, C.ay, C.ids.as<int32_t>(), C.cfirst.as<int64_t>(), C.cu.as<uint64_t>(),
                           C.cboff.as<int64_t>(), C.d_qc.as<int64_t>(), C.d_qb.as<int64_t>(), B.mini_pos.as<uint64_t>(),
                           B.mp_off.as<int64_t>(), B.d_qlen.as<int64_t>(), B.d_hash, B.rep_len.as<int32_t>(), B.idx->d_len,
                           B.n_q, B.opt, B.idx->k, z.p, rg.as<hymet_mm_reg>(), wv.as<int32_t>(), cov.as<uint64_t>(),

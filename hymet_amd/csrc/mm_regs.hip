@@ -60,7 +60,8 @@ __device__ void heap_sort(T *a, int64_t n, Less less) {
 
 struct RegParams {
     const uint64_t *ax, *ay;       // the chained anchor set
-    const int64_t *ids, *cfirst;   // backtrack output (chains end -> start) and each chain's first slot in it
+    const int32_t *ids;            // backtrack output (chains end -> start)
+    const int64_t *cfirst;         // each chain's first slot in it
     const uint64_t *cu;            // score<<32 | count per chain
     const int64_t *cboff;          // chain -> offset of its anchors in chain order (region `as`)
     const int64_t *qc;             // n_q + 1 chain offsets
@@ -112,7 +113,8 @@ __device__ void set_coor(hymet_mm_reg *r, int32_t qlen, uint64_t x0, uint64_t y0
 
 struct AnchorStatParams {
     const uint64_t *ax, *ay, *cu;
-    const int64_t *ids, *cfirst;  // backtrack output (chains end -> start), each chain's first slot in it
+    const int32_t *ids;           // backtrack output (chains end -> start)
+    const int64_t *cfirst;        // each chain's first slot in it
     const int64_t *cboff, *qb, *qlen, *mp_off;
     const uint64_t *mini_pos;
     int64_t NB, NC;
@@ -1149,7 +1151,7 @@ __global__ void chain_stats_init_kernel(int32_t *c_mlen, int32_t *c_blen, int32_
 
 }  // namespace
 
-int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const int64_t *ids, const int64_t *cfirst,
+int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const int32_t *ids, const int64_t *cfirst,
                    const uint64_t *cu, const int64_t *cboff,
                    const int64_t *qc, const int64_t *qb, const uint64_t *mini_pos, const int64_t *mp_off, const int64_t *qlen,
                    const uint32_t *name_hash, const int32_t *rep_len, const int64_t *ref_len, int n_q, const hymet_mm_opt *o,
@@ -1163,8 +1165,8 @@ int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const
     int32_t *c_mlen = cst.as<int32_t>(), *c_blen = c_mlen + (NC + 1), *c_st = c_blen + (NC + 1), *c_last = c_st + (NC + 1),
             *c_fv = c_last + (NC + 1);
     {
-        // chain slot (8) + anchor x, y (16) + its minimizer-table read (4: 16 B per 64 bases) per chained anchor
-        ProfScope _ps(ctx, "mm_chain_stats", (double)NB * (8.0 + 16.0 + 4.0) + (double)NM * 8.0);
+        // chain slot (4) + anchor x, y (16) + its minimizer-table read (4: 16 B per 64 bases) per chained anchor
+        ProfScope _ps(ctx, "mm_chain_stats", (double)NB * (4.0 + 16.0 + 4.0) + (double)NM * 8.0);
         AnchorStatParams A{ax, ay, cu, ids, cfirst, cboff, qb, qlen, mp_off, mini_pos, NB, NC, n_q, cq,
                            c_mlen, c_blen, c_st, c_last, mtab, qbase, skip_q};
         if (NB > 0) {

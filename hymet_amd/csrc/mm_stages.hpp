@@ -56,6 +56,11 @@ inline int scan_flags(hymet_ctx *ctx, const uint32_t *flag, int64_t n, DevBuf &p
     return exclusive_scan_u32_i64(ctx, flag, pos.as<int64_t>(), n, total);
 }
 
+// The most anchors a set may hold: the DP's links p and the backtrack's chain ids are 32-bit
+// indices into their set (n < INT32_MAX).  HYMET_ANCHOR_CAP lowers it, so a test reaches the
+// error with a small input.
+inline int64_t anchor_cap() { return env_int("HYMET_ANCHOR_CAP", INT32_MAX - 1, 1, INT32_MAX - 1); }
+
 // An anchor set sorted by (query, x, y): arrays + per-query offsets (device + host).
 struct AnchorSet {
     DevBuf ax, ay;

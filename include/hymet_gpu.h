@@ -368,18 +368,19 @@ int hymet_emit_paf(hymet_ctx *ctx, const hymet_paf_acc *acc, const uint8_t *d_qn
  * parity tests and kernel timing: n anchors (x, y as minimap2 packs them) of ONE query,
  * sorted by x; groups are runs of equal x>>32.  max_dist/bw are given as mg_lchain_rmq
  * receives them (first pass: max_gap, bw; long join: max_gap, bw_long).  Host arrays,
- * synchronous; h_p holds anchor indices or -1. */
+ * synchronous; h_p holds anchor indices or -1 (32-bit links on the device, widened on copy-out). */
 int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, int64_t n, int max_dist,
                       int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap,
                       float pen_skip, int32_t *h_f, int64_t *h_p);
 /* The grouped anchor sort alone (the stage inside hymet_mm_map that puts a batch's anchor
  * keys in minimap2's order), for parity tests: n keys (query | strand | target in rb bits |
  * target position in pb bits) with values y, query-major, query q's at [h_qoff[q],
- * h_qoff[q+1]); max_qlen bounds y.  Returns the anchor set in (key, y) order -- h_ax =
+ * h_qoff[q+1]); max_qlen bounds y (a y of more bits than max_qlen has: HYMET_E_ARG).  Returns the anchor set in (key, y) order -- h_ax =
  * strand<<63 | target<<32 | position, h_ay = yhi<<32 | y, h_ax32 = position -- and the head
  * bitmap h_hb ((n + 31) / 32 words: bit i set where anchor i starts a (query, strand, target)
- * group).  Returns 1, nothing written, where the grouped sort does not apply (the packed
- * words would pass 64 bits).  h_stats (nullable, 4 entries): segments and anchors the block
+ * group).  The pairs are packed on the device into the stage's input, one 64-bit anchor word
+ * (strand | target | position) << ybits | y each.  Returns 1, nothing written, where the
+ * grouped sort does not apply (the word would pass 63 bits).  h_stats (nullable, 4 entries): segments and anchors the block
  * sorts finished by their outlier path, segments and anchors that took their full sort.
  * Host arrays, synchronous. */
 int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const uint32_t *h_val, int64_t n,

@@ -39,7 +39,8 @@ int main(int argc, char **argv) {
     std::vector<uint64_t> hx(n), hy(n);
     for (int64_t i = 0; i < n; i++) hx[i] = a[2 * i], hy[i] = a[2 * i + 1];
     uint64_t *dx, *dy;
-    int64_t *gs, *dp;
+    int64_t *gs;
+    int32_t *dp;
     int32_t *order, *cnt, *df, *dt;
     uint8_t *qf;
     int4 *sum;
@@ -47,7 +48,7 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&dx, 8 * n));
     CK(hipMalloc(&dy, 8 * n));
     CK(hipMalloc(&gs, 16));
-    CK(hipMalloc(&dp, 8 * n));
+    CK(hipMalloc(&dp, 4 * n));
     CK(hipMalloc(&order, 4));
     CK(hipMalloc(&cnt, 4 * kChainCtrPad * kChainStripes));  // the striped work counters (zeroed by the split kernel)
     CK(hipMalloc(&df, 4 * n));
@@ -119,7 +120,7 @@ int main(int argc, char **argv) {
 #endif
         CK(hipMemset(cnt, 0, 4));
         CK(hipMemset(df, 0, 4 * n));
-        CK(hipMemset(dp, 0xFF, 8 * n));
+        CK(hipMemset(dp, 0xFF, 4 * n));
         CK(hipMemset(dt, 0, 4 * n));  // t arrives zeroed (overflow stamps are i + 1)
         ChainParams P{dx32, dy, gs, qf, order, nwork, cnt, df, dp, dt, sum, max_dist, 1000, bw, 25, 100000, 0.12f, 0.0f, nullptr};
         hipEvent_t e0, e1;
@@ -181,11 +182,11 @@ int main(int argc, char **argv) {
 #endif
         {  // f / p digest: variants must agree bit for bit
             std::vector<int32_t> hf(n);
-            std::vector<int64_t> hp(n);
+            std::vector<int32_t> hp(n);
             CK(hipMemcpy(hf.data(), df, 4 * n, hipMemcpyDeviceToHost));
-            CK(hipMemcpy(hp.data(), dp, 8 * n, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(hp.data(), dp, 4 * n, hipMemcpyDeviceToHost));
             uint64_t h = 1469598103934665603ull;
-            for (int64_t i = 0; i < n; i++) h = (h ^ (uint64_t)(uint32_t)hf[i]) * 1099511628211ull, h = (h ^ (uint64_t)hp[i]) * 1099511628211ull;
+            for (int64_t i = 0; i < n; i++) h = (h ^ (uint64_t)(uint32_t)hf[i]) * 1099511628211ull, h = (h ^ (uint64_t)(int64_t)hp[i]) * 1099511628211ull;
             printf("fp digest %016llx\n", (unsigned long long)h);
         }
         const char *names[8] = {"i0-advance", "st+head", "st_in", "rmq", "walk", "winner+cert", "st_in-probe", "loop/batch"};
