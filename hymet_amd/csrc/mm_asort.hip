@@ -80,9 +80,9 @@ __device__ __forceinline__ int seg_class_group(int64_t n) {
 // bitmap instead of re-reading x (hb zeroed by grouped_anchor_sort; a word may straddle two
 // writers' segments, hence the atomic)
 struct AnchorOut {
-    uint64_t *ax, *ay;
+    uint64_t *ax;
+    uint32_t *ay;  // y's low word: the high word (the span) is the set's constant, kept beside the set
     int rb, pb, ybits;
-    uint64_t yhi;
     uint32_t *hb;
     uint32_t *ax32;  // x's low word (rpos) alone: the chaining kernels' reads, 4 B per anchor instead of 8
     // the anchor of word w = (rev | rid | rpos) << ybits | y
@@ -90,7 +90,7 @@ struct AnchorOut {
         const uint64_t k = w >> ybits, y = w & ((1ull << ybits) - 1);
         const uint64_t rev = k >> (rb + pb) & 1, rid = k >> pb & ((1ull << rb) - 1), rpos = k & ((1ull << pb) - 1);
         ax[i] = rev << 63 | rid << 32 | rpos;
-        ay[i] = yhi << 32 | y;
+        ay[i] = (uint32_t)y;
         ax32[i] = (uint32_t)rpos;
     }
     // w written at i, wp at i - 1 (first: i starts a writer's segment -- a query or a bin, a
@@ -910,7 +910,7 @@ int sort_segments(hymet_ctx *ctx, const Seg *lists, int64_t cap, const int32_t *
 }  // namespace
 
 int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, int64_t n, const int64_t *d_qoff, int n_q, int rb, int pb,
-                        uint64_t yhi, int64_t max_qlen, uint64_t *okey, uint64_t *ax, uint64_t *ay, uint32_t *hb,
+                        int64_t max_qlen, uint64_t *okey, uint64_t *ax, uint32_t *ay, uint32_t *hb,
                         uint32_t *ax32, unsigned long long *d_stats) {
     // bins = (strand, target) -- or, for parts of more than 2047 targets, (strand, target >> cs):
     // coarse bins of 2^cs consecutive targets, sorted inside by (low target bits, rpos, y)
@@ -920,7 +920,7 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, int64_t n, const in
     const int ybits = anchor_word_ybits(rb, pb, max_qlen);
     if (n <= 0 || n_q <= 0 || ybits == 0) return 1;
     hipStream_t st = ctx->stream;
-    const AnchorOut out{ax, ay, rb, pb, ybits, yhi, hb, ax32};
+    const AnchorOut out{ax, ay, rb, pb, ybits, hb, ax32};
     HY_HIP(hipMemsetAsync(hb, 0, head_bits_bytes(n), st));
     // 1 queries by size
     DevBuf qlists, nt;
@@ -935,8 +935,8 @@ int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *key, int64_t n, const in
         hq[c] = (int32_t)mb_read(ctx, kMbQClass + c);
         if (hq[c] < 0 || hq[c] > n_q) return hymet::fail(HYMET_E_INTERNAL, "grouped_anchor_sort: query class count > cap");
     }
-    // word read by the histogram and by the scatter, scatter write, sort read, x + y + x32 write
-    ProfScope _ps(ctx, "mm_anchor_gsort", 52.0 * (double)n);
+    // word read by the histogram and by the scatter, scatter write, sort read, x + y (4 B) + x32 write
+    ProfScope _ps(ctx, "mm_anchor_gsort", 48.0 * (double)n);
     // 2 small queries: sorted whole
     int rc = sort_segments(ctx, qlists.as<Seg>(), n_q, hq, key, 1 + rb + pb + ybits, out, d_stats);
     if (rc || hq[kLarge] == 0) return rc;
@@ -1052,7 +1052,7 @@ extern "C" int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const
     HY_HIP(word.alloc(8 * (size_t)n, st));
     HY_HIP(okey.alloc(8 * (size_t)n, st));
     HY_HIP(ax.alloc(8 * (size_t)n, st));
-    HY_HIP(ay.alloc(8 * (size_t)n, st));
+    HY_HIP(ay.alloc(4 * (size_t)n, st));
     HY_HIP(ax32.alloc(4 * (size_t)n, st));
     HY_HIP(hb.alloc(hb_bytes, st));
     HY_HIP(stats.alloc(8 * hymet::mm::kStats, st));
@@ -1063,8 +1063,8 @@ extern "C" int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const
     hipLaunchKernelGGL(hymet::mm::pack_words_kernel, dim3((unsigned)hymet::cdiv(n, 256)), dim3(256), 0, st, key.as<uint64_t>(),
                        val.as<uint32_t>(), n, 1 + rb + pb, ybits, word.as<uint64_t>());
     HY_CHECK_LAUNCH("pack_words_kernel");
-    const int rc = hymet::mm::grouped_anchor_sort(ctx, word.as<uint64_t>(), n, qoff.as<int64_t>(), n_q, rb, pb, yhi, max_qlen,
-                                                  okey.as<uint64_t>(), ax.as<uint64_t>(), ay.as<uint64_t>(),
+    const int rc = hymet::mm::grouped_anchor_sort(ctx, word.as<uint64_t>(), n, qoff.as<int64_t>(), n_q, rb, pb, max_qlen,
+                                                  okey.as<uint64_t>(), ax.as<uint64_t>(), ay.as<uint32_t>(),
                                                   hb.as<uint32_t>(), ax32.as<uint32_t>(),
                                                   h_stats ? stats.as<unsigned long long>() : nullptr);
     if (rc) {
@@ -1072,10 +1072,12 @@ extern "C" int hymet_mm_anchor_sort(hymet_ctx *ctx, const uint64_t *h_key, const
         return rc;
     }
     HY_HIP(hipMemcpyAsync(h_ax, ax.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
-    HY_HIP(hipMemcpyAsync(h_ay, ay.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> y32((size_t)n);  // y is 32-bit on the device: widened with the span for the caller
+    HY_HIP(hipMemcpyAsync(y32.data(), ay.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HY_HIP(hipMemcpyAsync(h_ax32, ax32.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HY_HIP(hipMemcpyAsync(h_hb, hb.p, 4 * (size_t)((n + 31) / 32), hipMemcpyDeviceToHost, st));
     if (h_stats) HY_HIP(hipMemcpyAsync(h_stats, stats.p, 8 * hymet::mm::kStats, hipMemcpyDeviceToHost, st));
     HY_HIP(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n; i++) h_ay[i] = yhi << 32 | y32[(size_t)i];
     return HYMET_OK;
 }

@@ -147,7 +147,8 @@ constexpr int kChainStripes = HYMET_CHAIN_STRIPES, kChainCtrPad = 64;
 
 struct ChainParams {
     const int32_t *ax;        // x's low word (target position) per anchor: x >> 32 is the group's constant
-    const uint64_t *ay;
+    const uint32_t *ay;       // y's low word (query position) per anchor
+    int32_t span;             // y's high word: the query span, one value for the whole set
     const int64_t *g_start;   // group g = anchors [g_start[g], g_start[g+1])
     const uint8_t *g_qfirst;  // group g starts its query's anchor array (the krmq index-0 quirk)
     const int32_t *order;     // work list of group ids (size-descending)
@@ -421,8 +422,7 @@ __device__ __forceinline__ void chain_mid_group(const ChainParams &P, int64_t g0
     const int lane = threadIdx.x;
     const bool act = lane < n;
     const int jl = act ? lane : n - 1;
-    const uint64_t yv = P.ay[g0 + jl];
-    const int32_t X = P.ax[g0 + jl], Y = (int32_t)yv, SP = (int32_t)(yv >> 32 & 0xff);
+    const int32_t X = P.ax[g0 + jl], Y = (int32_t)P.ay[g0 + jl], SP = P.span;
     // walk order: the anchors by (y, idx) descending; lane w of the walk holds anchor wa
     int rank = 0;
     for (int m = 0; m < n; ++m) {
@@ -555,6 +555,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
     int32_t *xring = reinterpret_cast<int32_t *>(sp);  // x of anchor j at [j & (kXRing - 1)]
     sp += kXRing * sizeof(int32_t);
     const double c = 0.5 * (double)P.pen_gap;
+    const int32_t span_pw = (int32_t)((uint32_t)P.span << 24);  // the span as an entry's pw carries it
     const int32_t n_work = P.work_end ? min(P.n_work, *P.work_end) : P.n_work;
     // work list dealt over kChainStripes counters on separate lines (stripe s: positions
     // s + kChainStripes t), as in backtrack_long_kernel: one returning atomic per group on a
@@ -598,8 +599,8 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             } else {
                 CCOUNT(0);
                 const int32_t x = P.ax[g0 + jl];
-                const uint64_t y = P.ay[g0 + jl];
-                v = make_int4(x, (int32_t)y, ld_l2(P.f + g0 + jl), (int32_t)((uint32_t)(y >> 32 & 0xff) << 24));
+                const int32_t y = (int32_t)P.ay[g0 + jl];
+                v = make_int4(x, y, ld_l2(P.f + g0 + jl), span_pw);
             }
             e.x = v.x, e.y = v.y, e.f = v.z, e.pw = v.w;
             return e;
@@ -612,10 +613,9 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                 v = ring[jl & kRingMask];
             } else {
                 const int32_t x = P.ax[g0 + jl];
-                const uint64_t y = P.ay[g0 + jl];
+                const int32_t y = (int32_t)P.ay[g0 + jl];
                 const int64_t pp = ld_l2(P.p + g0 + jl);
-                v = make_int4(x, (int32_t)y, ld_l2(P.f + g0 + jl),
-                              (int32_t)((pp < 0 ? 0u : (uint32_t)(pp - g0 + 1)) | (uint32_t)(y >> 32 & 0xff) << 24));
+                v = make_int4(x, y, ld_l2(P.f + g0 + jl), (int32_t)(pp < 0 ? 0u : (uint32_t)(pp - g0 + 1)) | span_pw);
             }
             e.x = v.x, e.y = v.y, e.f = v.z, e.pw = v.w;
             return e;
@@ -719,15 +719,15 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
         __builtin_amdgcn_wave_barrier();
         // anchor chunks in registers, lane l holding anchor (chunk base + l): the current one
         // (cx, cy), the next (nx, ny) and the one after (nnx, nny).  Only x's low word is kept
-        // (x >> 32 is the group's constant); y keeps the query span in bits 32..39.
+        // (x >> 32 is the group's constant) and y's (the span is the set's constant).
         int32_t cx = 0, nx = 0, nnx = 0;
-        uint64_t cy = 0, ny = 0, nny = 0;
+        int32_t cy = 0, ny = 0, nny = 0;
         // unconditional loads (index clamped to the group): a `b < n ? load : 0` select made
         // the compiler land each prefetch in a temporary and wait for it (vmcnt) to copy it
         // into place, so the prefetch was synchronous.  Lanes past the group end hold copies of
         // its last anchor, which nothing reads (batches stop at the group end).
         auto ldx = [&](int32_t b) -> int32_t { return P.ax[g0 + min(b, n - 1)]; };
-        auto ldy = [&](int32_t b) -> uint64_t { return P.ay[g0 + min(b, n - 1)]; };
+        auto ldy = [&](int32_t b) -> int32_t { return (int32_t)P.ay[g0 + min(b, n - 1)]; };
         Ent prev{0, 0, 0, 0};  // anchor i-1
         // block b complete: staircase summary -- S1 = argmin, S(k+1) = argmin over y < y(Sk),
         // i.e. the entries better than every entry with y <= theirs, by y descending; the
@@ -889,9 +889,9 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             // the merge's phi copies, placed after the loads -- which then had to land in
             // temporaries and be waited for (vmcnt) before the copy
             asm volatile("v_mov_b32 %0, %1" : "=v"(cx) : "v"(nx));
-            asm volatile("v_mov_b64 %0, %1" : "=v"(cy) : "v"(ny));
+            asm volatile("v_mov_b32 %0, %1" : "=v"(cy) : "v"(ny));
             asm volatile("v_mov_b32 %0, %1" : "=v"(nx) : "v"(nnx));
-            asm volatile("v_mov_b64 %0, %1" : "=v"(ny) : "v"(nny));
+            asm volatile("v_mov_b32 %0, %1" : "=v"(ny) : "v"(nny));
             cb = ii & ~63;
             nnx = ldx(cb + 128 + lane), nny = ldy(cb + 128 + lane);
         };
@@ -906,8 +906,8 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             CPROF(7);
             advance(i);
             const int32_t xi = rl(cx, i & 63);
-            const int32_t yi = rl((int32_t)cy, i & 63);
-            const int32_t span_i = rl((int32_t)(cy >> 32 & 0xff), i & 63);
+            const int32_t yi = rl(cy, i & 63);
+            const int32_t span_i = P.span;
             int32_t max_f = span_i;
             int32_t max_j = -1;
             // ---- 1. i0 advances: insert [i0, i) into the window structures
@@ -1181,11 +1181,10 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                     // anchors k = i + lane from the chunk registers (cx: [cb, cb+64), nx: next 64)
                     const int off = (i - cb) + lane;
                     const int32_t kx_lo = __shfl(cx, off & 63, 64), kx_hi = __shfl(nx, off & 63, 64);
-                    const uint64_t ky_lo = __shfl(cy, off & 63, 64), ky_hi = __shfl(ny, off & 63, 64);
+                    const int32_t ky_lo = __shfl(cy, off & 63, 64), ky_hi = __shfl(ny, off & 63, 64);
                     const bool inb = lane < Lb;
                     const int32_t kx = off < 64 ? kx_lo : kx_hi;
-                    const uint64_t kyy = off < 64 ? ky_lo : ky_hi;
-                    const int32_t ky = (int32_t)kyy, ksp = (int32_t)(kyy >> 32 & 0xff);
+                    const int32_t ky = off < 64 ? ky_lo : ky_hi, ksp = P.span;
                     const int32_t px = shr1(kx, e0.x), py = shr1(ky, e0.y), psp = shr1(ksp, e0.sp());
                     int32_t ex = 1, wd = 0;
                     const int32_t s = comput_sc(kx, ky, px, py, psp, P.pen_gap, P.pen_skip, &ex, &wd);
@@ -1288,7 +1287,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                         // commit anchors [i, i + acc): f, p, ring; insert entries [i, i + acc - 1)
                         const int32_t k = i + lane;
                         const int32_t pk_local = linked ? (lane == 0 ? b0j : k - 1) : -1;
-                        const int32_t pw = (int32_t)((uint32_t)(pk_local + 1) | (uint32_t)ksp << 24);
+                        const int32_t pw = (int32_t)((uint32_t)(pk_local + 1) | (uint32_t)span_pw);
                         if (lane < acc) {
                             ring[k & kRingMask] = make_int4(kx, ky, fk, pw);
                             xring[k & (kXRing - 1)] = kx;
@@ -1533,7 +1532,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             // stamps only ever land on earlier anchors, and are cleared at the group's end)
             P.f[g0 + i] = max_f;
             P.p[g0 + i] = max_j < 0 ? -1 : (int32_t)(g0 + max_j);
-            prev.x = xi, prev.y = yi, prev.f = max_f, prev.pw = (int32_t)((uint32_t)(max_j + 1) | (uint32_t)span_i << 24);
+            prev.x = xi, prev.y = yi, prev.f = max_f, prev.pw = (int32_t)((uint32_t)(max_j + 1) | (uint32_t)span_pw);
             if (lane == 0) {
                 ring[i & kRingMask] = make_int4(prev.x, prev.y, prev.f, prev.pw);
                 xring[i & (kXRing - 1)] = prev.x;
@@ -2035,11 +2034,10 @@ __global__ __launch_bounds__(64) void chain_small_kernel(ChainParams P, const in
     const int n = (int)(P.g_start[g + 1] - g0);
     const bool qfirst = P.g_qfirst[g] != 0;
     const double c = 0.5 * (double)P.pen_gap;
-    int32_t X[kSmall], Y[kSmall], SP[kSmall], F[kSmall], PJ[kSmall], T[kSmall];
+    int32_t X[kSmall], Y[kSmall], F[kSmall], PJ[kSmall], T[kSmall];
     int8_t ord[kSmall];  // local indices by (y, idx) ascending
     for (int j = 0; j < n; ++j) {
-        const uint64_t y = P.ay[g0 + j];
-        X[j] = P.ax[g0 + j], Y[j] = (int32_t)y, SP[j] = (int32_t)(y >> 32 & 0xff);
+        X[j] = P.ax[g0 + j], Y[j] = (int32_t)P.ay[g0 + j];
         F[j] = 0, PJ[j] = -1, T[j] = -1;
         int k = j;  // insertion by (y, idx): later j is the larger idx, so ties stay behind
         while (k > 0 && Y[ord[k - 1]] > Y[j]) {
@@ -2052,7 +2050,7 @@ __global__ __launch_bounds__(64) void chain_small_kernel(ChainParams P, const in
     int size_out = 0, size_in = 0, i0 = 0, st = 0, st_in = 0;
     for (int i = 0; i < n; ++i) {
         const int32_t xi = X[i], yi = Y[i];
-        int32_t max_f = SP[i], max_j = -1;
+        int32_t max_f = P.span, max_j = -1;
         if (i0 < i && X[i0] != xi) {
             for (int j = i0; j < i; ++j) {
                 in_out |= 1u << j, size_out++;
@@ -2084,7 +2082,7 @@ __global__ __launch_bounds__(64) void chain_small_kernel(ChainParams P, const in
         }
         if (bj >= 0) {
             int32_t exact, width;
-            const int32_t sc = F[bj] + comput_sc(xi, yi, X[bj], Y[bj], SP[bj], P.pen_gap, P.pen_skip, &exact, &width);
+            const int32_t sc = F[bj] + comput_sc(xi, yi, X[bj], Y[bj], P.span, P.pen_gap, P.pen_skip, &exact, &width);
             if (width <= P.bw && sc > max_f) max_f = sc, max_j = bj;
             if (!exact && size_in > 0 && yi > 0) {
                 const int32_t ylo_in = yi - P.max_dist_inner;
@@ -2096,7 +2094,7 @@ __global__ __launch_bounds__(64) void chain_small_kernel(ChainParams P, const in
                     if (Y[jj] < ylo_in) break;
                     if (!(in_in >> jj & 1)) continue;
                     int32_t ex2, w2;
-                    const int32_t sc2 = F[jj] + comput_sc(xi, yi, X[jj], Y[jj], SP[jj], P.pen_gap, P.pen_skip, &ex2, &w2);
+                    const int32_t sc2 = F[jj] + comput_sc(xi, yi, X[jj], Y[jj], P.span, P.pen_gap, P.pen_skip, &ex2, &w2);
                     if (w2 <= P.bw) {
                         if (sc2 > max_f) {
                             max_f = sc2, max_j = jj;
@@ -2132,7 +2130,7 @@ int launch_chain_raw(hipStream_t st, const ChainParams &P0, int64_t blocks, int3
     return HYMET_OK;
 }
 
-int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const int64_t *g_start, const uint8_t *g_qfirst,
+int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint32_t *ay, int span, const int64_t *g_start, const uint8_t *g_qfirst,
                  const int32_t *order, int32_t n_work, int32_t *f, int32_t *p, int32_t *t_global, int max_dist,
                  int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap, float pen_skip,
                  int64_t n_anchors, int64_t n_groups) {
@@ -2144,7 +2142,7 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const in
     HY_HIP(split.alloc(4, ctx->stream));
     if (max_dist < bw) max_dist = bw;
     if (max_dist_inner <= 0 || max_dist_inner >= max_dist) max_dist_inner = 0;
-    ChainParams P{ax, ay, g_start, g_qfirst, order, n_work, cnt.as<int32_t>(), f, p, t_global, sum.as<int4>(), max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, pen_gap, pen_skip, nullptr};
+    ChainParams P{ax, ay, span, g_start, g_qfirst, order, n_work, cnt.as<int32_t>(), f, p, t_global, sum.as<int4>(), max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, pen_gap, pen_skip, nullptr};
     // one wave per block, as many resident per CU as registers and LDS allow
     int64_t blocks = n_work;
     int per_cu = 0;
@@ -2157,14 +2155,14 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const in
     const int64_t cap = (int64_t)ctx->n_cu * per_cu;
     if (blocks > cap) blocks = cap;
     // two profile scopes, one kernel each: the wave kernel (groups above kSmall anchors, the
-    // mid-group path included) and the lane kernel; each scope's algorithmic bytes are 28 per
+    // mid-group path included) and the lane kernel; each scope's algorithmic bytes are 24 per
     // anchor it chains, counted on the device from the work list (x, y read; f, p written, with
-    // the 64-bit x and p these kernels began with: the benchmark's text names the 28, so the
-    // constant stays though x's low word and a 32-bit p make it 20)
+    // the 64-bit x and p these kernels began with and a 32-bit y: the model followed y's width
+    // down from 28, though x's low word and a 32-bit p make the real figure 16)
     const int slot = long_pass ? 2 : 0;
     hipStream_t st = ctx->stream;
     {
-        ProfScope _ps(ctx, long_pass ? "mm_chain_long" : "mm_chain", slot, 28.0);
+        ProfScope _ps(ctx, long_pass ? "mm_chain_long" : "mm_chain", slot, 24.0);
         hipLaunchKernelGGL(chain_small_split_kernel, dim3(1), dim3(64), 0, st, P.g_start, P.order, P.n_work,
                            split.as<int32_t>(), P.work_counter, long_pass ? kSmallLong : kSmall);
         HY_CHECK_LAUNCH("chain_small_split_kernel");
@@ -2179,7 +2177,7 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const in
         else hipLaunchKernelGGL(chain_groups_kernel<0>, dim3((unsigned)blocks), dim3(64), kChainLds, st, P);
         HY_CHECK_LAUNCH("chain_groups_kernel");
     }
-    ProfScope _pl(ctx, long_pass ? "mm_chain_long_small" : "mm_chain_small", slot + 1, 28.0);
+    ProfScope _pl(ctx, long_pass ? "mm_chain_long_small" : "mm_chain_small", slot + 1, 24.0);
     hipLaunchKernelGGL(chain_small_kernel, dim3((unsigned)cdiv(P.n_work, 64)), dim3(64), 0, st, P, (const int32_t *)split.as<int32_t>());
     HY_CHECK_LAUNCH("chain_small_kernel");
     return HYMET_OK;

@@ -13,7 +13,7 @@
 namespace hymet {
 namespace mm {
 
-int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint64_t *ay, const int64_t *g_start, const uint8_t *g_qfirst,
+int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint32_t *ay, int span, const int64_t *g_start, const uint8_t *g_qfirst,
                  const int32_t *order, int32_t n_work, int32_t *f, int32_t *p, int32_t *t_global, int max_dist,
                  int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap, float pen_skip,
                  int64_t n_anchors, int64_t n_groups);
@@ -566,7 +566,7 @@ __global__ void chain_cnt_kernel(const uint64_t *cu, const uint32_t *cq, const u
 // long join, first pass (map.c's rmq rescue): a query is re-chained when it has more than one
 // chain and its first chain (compact order) leaves too much of it uncovered -- read from the
 // chain list before the copy
-__global__ void rechain_flag_kernel(const uint64_t *ay, const int32_t *chain_ids, const uint64_t *cu, const int64_t *cfirst,
+__global__ void rechain_flag_kernel(const uint32_t *ay, const int32_t *chain_ids, const uint64_t *cu, const int64_t *cfirst,
                                     const int64_t *qc, const int64_t *qlen, int n_q, int rescue_size, float rescue_ratio,
                                     uint32_t *flag) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -594,10 +594,10 @@ __global__ void chain_qb_kernel(const int64_t *qc, const int64_t *bpos, int64_t 
 // anchors of chain c in start -> end order, and c per anchor (the chains of queries the long
 // join re-chains have no anchors here: cnt 0)
 __global__ __launch_bounds__(256) void chain_copy_kernel(const uint64_t *cu, const int64_t *cfirst, const int64_t *bpos,
-                                                         const int32_t *chain_ids, const uint64_t *ax, const uint64_t *ay,
-                                                         int64_t n_chain, int64_t nb, uint64_t *bx, uint64_t *by,
+                                                         const int32_t *chain_ids, const uint64_t *ax, const uint32_t *ay,
+                                                         int64_t n_chain, int64_t nb, uint64_t *bx, uint32_t *by,
                                                          int32_t *bchain) {
-    // flat over the output anchors (~48 B each, bandwidth-bound: C4 copies ~236 M per batch at
+    // flat over the output anchors (~40 B each, bandwidth-bound: C4 copies ~236 M per batch at
     // ~3.8 TB/s): the block's first chain c0 by binary search over bpos; the starts of the next
     // 256 chains are staged in LDS and each lane finds its chain by an 8-step search there (a
     // forward walk per lane cost up to 255 dependent loads where chains are short).  Chains
@@ -719,8 +719,8 @@ __global__ __launch_bounds__(256) void mark_count_kernel(const int32_t *t, int64
 // anchor of an earlier tile (last_kept, from the count).
 __global__ __launch_bounds__(256) void mark_compact_kernel(const int32_t *t, int64_t n, const uint32_t *qflag,
                                                            const int64_t *qoff, int n_q, const int64_t *tile_off,
-                                                           const int64_t *last_kept, const uint64_t *ax, const uint64_t *ay,
-                                                           uint64_t *ox, uint64_t *oy, uint32_t *ohb, uint32_t *ox32) {
+                                                           const int64_t *last_kept, const uint64_t *ax, const uint32_t *ay,
+                                                           uint64_t *ox, uint32_t *oy, uint32_t *ohb, uint32_t *ox32) {
     __shared__ uint32_t rc[64];       // kept per (row, wave), row-major
     __shared__ uint32_t nk[64];       // the same counts (rc becomes their exclusive scan)
     __shared__ uint32_t lx[64];       // x >> 32 of each (row, wave) chunk's last kept anchor
@@ -911,7 +911,7 @@ static int chain_dp(hymet_ctx *ctx, const DpArgs &a, const AnchorSet &A, const G
     HY_HIP(p.alloc(4 * (size_t)A.n, ctx->stream));
     LAUNCH1(nonwork_fp_kernel, Gr.G, Gr.g_start.as<int64_t>(), (int32_t)Gr.G, a.min_cnt, f.as<int32_t>(), p.as<int32_t>(),
             t.as<int32_t>());
-    return launch_chain(ctx, A.ax32.as<int32_t>(), A.ay.as<uint64_t>(), Gr.g_start.as<int64_t>(), Gr.qfirst.as<uint8_t>(),
+    return launch_chain(ctx, A.ax32.as<int32_t>(), A.ay.as<uint32_t>(), A.span, Gr.g_start.as<int64_t>(), Gr.qfirst.as<uint8_t>(),
                         W.order.as<int32_t>(), (int32_t)W.n_work, f.as<int32_t>(), p.as<int32_t>(), t.as<int32_t>(), a.max_dist,
                         a.max_dist_inner, a.bw, a.max_chn_skip, a.cap_rmq_size, a.pen_gap, a.pen_skip, A.n, Gr.G);
 }
@@ -1045,7 +1045,7 @@ static int chain_layout(hymet_ctx *ctx, const AnchorSet &A, int n_q, const DevBu
     const uint32_t *qflag = nullptr;
     if (lj) {
         HY_HIP(lj->flag.alloc(4 * (size_t)n_q, ctx->stream));
-        LAUNCH1(rechain_flag_kernel, n_q, A.ay.as<uint64_t>(), chain_ids.as<int32_t>(), C.cu.as<uint64_t>(),
+        LAUNCH1(rechain_flag_kernel, n_q, A.ay.as<uint32_t>(), chain_ids.as<int32_t>(), C.cu.as<uint64_t>(),
                 cfirst.as<int64_t>(), C.d_qc.as<int64_t>(), lj->qlen, n_q, lj->rescue_size, lj->rescue_ratio,
                 lj->flag.as<uint32_t>());
         if (lj->mark_only) qflag = lj->flag.as<uint32_t>();
@@ -1062,12 +1062,12 @@ static int chain_layout(hymet_ctx *ctx, const AnchorSet &A, int n_q, const DevBu
     C.n_anchor = NB;
     if (copy) {
         HY_HIP(C.bx.alloc(8 * (size_t)(NB + 1), ctx->stream));
-        HY_HIP(C.by.alloc(8 * (size_t)(NB + 1), ctx->stream));
+        HY_HIP(C.by.alloc(4 * (size_t)(NB + 1), ctx->stream));
         HY_HIP(C.bchain.alloc(4 * (size_t)(NB + 1), ctx->stream));
         if (NC > 0 && NB > 0)
             LAUNCH1(chain_copy_kernel, NB, C.cu.as<uint64_t>(), cfirst.as<int64_t>(), C.cboff.as<int64_t>(),
-                    chain_ids.as<int32_t>(), A.ax.as<uint64_t>(), A.ay.as<uint64_t>(), NC, NB, C.bx.as<uint64_t>(),
-                    C.by.as<uint64_t>(), C.bchain.as<int32_t>());
+                    chain_ids.as<int32_t>(), A.ax.as<uint64_t>(), A.ay.as<uint32_t>(), NC, NB, C.bx.as<uint64_t>(),
+                    C.by.as<uint32_t>(), C.bchain.as<int32_t>());
     }
     HY_HIP(C.d_qb.alloc(8 * (size_t)(n_q + 1), ctx->stream));
     LAUNCH1(chain_qb_kernel, n_q + 1, C.d_qc.as<int64_t>(), C.cboff.as<int64_t>(), NC, NB, n_q, C.d_qb.as<int64_t>());
@@ -1090,7 +1090,7 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
               ChainSet &C, LeanJoin *lj, bool copy) {
     const int64_t n = A.n;
     HY_ARG(n >= 0 && n < INT32_MAX, "chain_set: an anchor set of 2^31 anchors or more (32-bit chain links)");
-    C.ax = A.ax.as<uint64_t>(), C.ay = A.ay.as<uint64_t>();
+    C.ax = A.ax.as<uint64_t>(), C.ay = A.ay.as<uint32_t>(), C.span = A.span;
     if (n == 0) {
         HY_HIP(C.d_qc.alloc(8 * (size_t)(n_q + 1), ctx->stream));
         HY_HIP(C.d_qb.alloc(8 * (size_t)(n_q + 1), ctx->stream));
@@ -1137,33 +1137,53 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
     return HYMET_OK;
 }
 
-int marked_anchor_set(hymet_ctx *ctx, const AnchorSet &S1, const LeanJoin &lj, const uint32_t *flag, int n_q, int64_t A2,
-                      AnchorSet &S2) {
+// the anchors of S1 with mark == 2 in flagged queries, compacted in S1's order into S2
+// (expect: their count as the caller knows it, or -1)
+static int compact_marked(hymet_ctx *ctx, const AnchorSet &S1, const int32_t *mark, const uint32_t *flag, int n_q,
+                          int64_t expect, AnchorSet &S2) {
     hipStream_t st = ctx->stream;
     const int64_t n1 = S1.n, nt = cdiv(n1, 4096);
     DevBuf tcnt, toff, tlast;
     HY_HIP(tcnt.alloc(4 * (size_t)(nt + 1), st));
     HY_HIP(toff.alloc(8 * (size_t)(nt + 1), st));
     HY_HIP(tlast.alloc(8 * (size_t)(nt + 1), st));
-    hipLaunchKernelGGL(mark_count_kernel, dim3((unsigned)nt), dim3(256), 0, st, lj.mark.as<int32_t>(), n1, flag,
+    hipLaunchKernelGGL(mark_count_kernel, dim3((unsigned)nt), dim3(256), 0, st, mark, n1, flag,
                        S1.d_off.as<int64_t>(), n_q, tcnt.as<uint32_t>(), tlast.as<int64_t>());
     HY_CHECK_LAUNCH("mark_count_kernel");
-    int64_t got = 0;
-    int rc = exclusive_scan_u32_i64(ctx, tcnt.as<uint32_t>(), toff.as<int64_t>(), nt, &got);
+    int64_t A2 = 0;
+    int rc = exclusive_scan_u32_i64(ctx, tcnt.as<uint32_t>(), toff.as<int64_t>(), nt, &A2);
     if (rc) return rc;
-    if (got != A2 || got != lj.n2) return hymet::fail(HYMET_E_INTERNAL, "hymet_mm_map: long-join anchor count mismatch");
+    if (expect >= 0 && A2 != expect) return hymet::fail(HYMET_E_INTERNAL, "hymet_mm_map: long-join anchor count mismatch");
     HY_HIP(S2.ax.alloc(8 * (size_t)(A2 + 1), st));
-    HY_HIP(S2.ay.alloc(8 * (size_t)(A2 + 1), st));
+    HY_HIP(S2.ay.alloc(4 * (size_t)(A2 + 1), st));
     HY_HIP(S2.hb.alloc(head_bits_bytes(A2), st));
     HY_HIP(S2.ax32.alloc(4 * (size_t)(A2 + 1), st));
     HY_HIP(hipMemsetAsync(S2.hb.p, 0, head_bits_bytes(A2), st));
-    hipLaunchKernelGGL(mark_compact_kernel, dim3((unsigned)nt), dim3(256), 0, st, lj.mark.as<int32_t>(), n1, flag,
+    hipLaunchKernelGGL(mark_compact_kernel, dim3((unsigned)nt), dim3(256), 0, st, mark, n1, flag,
                        S1.d_off.as<int64_t>(), n_q, toff.as<int64_t>(), tlast.as<int64_t>(), S1.ax.as<uint64_t>(),
-                       S1.ay.as<uint64_t>(), S2.ax.as<uint64_t>(), S2.ay.as<uint64_t>(), S2.hb.as<uint32_t>(),
+                       S1.ay.as<uint32_t>(), S2.ax.as<uint64_t>(), S2.ay.as<uint32_t>(), S2.hb.as<uint32_t>(),
                        S2.ax32.as<uint32_t>());
     HY_CHECK_LAUNCH("mark_compact_kernel");
     S2.n = A2;
+    S2.span = S1.span;
     S2.has_hb = S2.has_x32 = true;
+    return HYMET_OK;
+}
+
+int marked_anchor_set(hymet_ctx *ctx, const AnchorSet &S1, const LeanJoin &lj, const uint32_t *flag, int n_q, int64_t A2,
+                      AnchorSet &S2) {
+    if (A2 != lj.n2) return hymet::fail(HYMET_E_INTERNAL, "hymet_mm_map: long-join anchor count mismatch");
+    return compact_marked(ctx, S1, lj.mark.as<int32_t>(), flag, n_q, A2, S2);
+}
+
+// a caller's 64-bit y values as the device holds them: the low words, and the span they share
+static int narrow_y(const uint64_t *h_y, int64_t n, std::vector<uint32_t> &y32, int *span, const char *what) {
+    y32.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        if ((h_y[i] >> 32) != (h_y[0] >> 32)) return hymet::fail(HYMET_E_ARG, what);
+        y32[(size_t)i] = (uint32_t)h_y[i];
+    }
+    *span = n > 0 ? (int)(h_y[0] >> 32 & 0xff) : 0;
     return HYMET_OK;
 }
 
@@ -1184,13 +1204,16 @@ extern "C" int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint
     AnchorSet A;  // one query holding every anchor
     const int64_t h_off[2] = {0, n};
     A.n = n;
+    std::vector<uint32_t> y32;  // y is 32-bit on the device: narrowed for the upload
+    int rc = narrow_y(h_y, n, y32, &A.span, "hymet_mm_chain_dp: the anchors' y values carry different spans");
+    if (rc) return rc;
     HY_HIP(A.ax.alloc(8 * (size_t)n, st));
-    HY_HIP(A.ay.alloc(8 * (size_t)n, st));
+    HY_HIP(A.ay.alloc(4 * (size_t)n, st));
     HY_HIP(A.d_off.alloc(sizeof h_off, st));
     HY_HIP(hipMemcpyAsync(A.ax.p, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-    HY_HIP(hipMemcpyAsync(A.ay.p, h_y, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(A.ay.p, y32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
     HY_HIP(hipMemcpyAsync(A.d_off.p, h_off, sizeof h_off, hipMemcpyHostToDevice, st));
-    int rc = derive_heads(ctx, A);
+    rc = derive_heads(ctx, A);
     if (rc) return rc;
     Groups Gr;
     rc = build_groups(ctx, A, 1, Gr);
@@ -1208,5 +1231,49 @@ extern "C" int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint
     HY_HIP(hipMemcpyAsync(p32.data(), p.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HY_HIP(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; i++) h_p[i] = p32[(size_t)i];
+    return HYMET_OK;
+}
+
+extern "C" int hymet_mm_mark_compact(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, const int32_t *h_mark, int64_t n,
+                                     const int64_t *h_qoff, const uint32_t *h_qflag, int32_t n_q, uint64_t *h_ox,
+                                     uint64_t *h_oy, uint32_t *h_ohb, int64_t *n_kept) {
+    HY_ARG(ctx && h_x && h_y && h_mark && h_qoff && h_qflag && h_ox && h_oy && h_ohb && n_kept,
+           "hymet_mm_mark_compact: null argument");
+    HY_ARG(n > 0 && n < INT32_MAX && n_q > 0, "hymet_mm_mark_compact: n or n_q out of range");
+    HY_ARG(h_qoff[0] == 0 && h_qoff[n_q] == n, "hymet_mm_mark_compact: query offsets do not span the anchors");
+    for (int32_t q = 0; q < n_q; q++) HY_ARG(h_qoff[q] <= h_qoff[q + 1], "hymet_mm_mark_compact: query offsets not rising");
+    HY_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    AnchorSet S1, S2;
+    S1.n = n;
+    std::vector<uint32_t> y32;
+    int rc = narrow_y(h_y, n, y32, &S1.span, "hymet_mm_mark_compact: the anchors' y values carry different spans");
+    if (rc) return rc;
+    DevBuf mark, flag;
+    HY_HIP(S1.ax.alloc(8 * (size_t)n, st));
+    HY_HIP(S1.ay.alloc(4 * (size_t)n, st));
+    HY_HIP(S1.d_off.alloc(8 * (size_t)(n_q + 1), st));
+    HY_HIP(mark.alloc(4 * (size_t)n + 16, st));
+    HY_HIP(flag.alloc(4 * (size_t)n_q, st));
+    HY_HIP(hipMemcpyAsync(S1.ax.p, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(S1.ay.p, y32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(S1.d_off.p, h_qoff, 8 * (size_t)(n_q + 1), hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(mark.p, h_mark, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(flag.p, h_qflag, 4 * (size_t)n_q, hipMemcpyHostToDevice, st));
+    rc = compact_marked(ctx, S1, mark.as<int32_t>(), flag.as<uint32_t>(), n_q, -1, S2);
+    if (rc) {
+        HY_HIP(hipStreamSynchronize(st));  // the uploads read the caller's arrays
+        return rc;
+    }
+    const int64_t m = S2.n;
+    std::vector<uint32_t> oy32((size_t)m);
+    if (m > 0) {
+        HY_HIP(hipMemcpyAsync(h_ox, S2.ax.p, 8 * (size_t)m, hipMemcpyDeviceToHost, st));
+        HY_HIP(hipMemcpyAsync(oy32.data(), S2.ay.p, 4 * (size_t)m, hipMemcpyDeviceToHost, st));
+        HY_HIP(hipMemcpyAsync(h_ohb, S2.hb.p, 4 * (size_t)((m + 31) / 32), hipMemcpyDeviceToHost, st));
+    }
+    HY_HIP(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < m; i++) h_oy[i] = (h_y[0] >> 32) << 32 | oy32[(size_t)i];
+    *n_kept = m;
     return HYMET_OK;
 }

@@ -161,13 +161,14 @@ inline int anchor_word_ybits(int rb, int pb, int64_t max_qlen) {
     return yb <= 32 && 1 + rb + pb + yb <= 63 ? yb : 0;
 }
 // Per-query grouped sort of anchor words (mm_asort.hip): word (n, query-major, query offsets
-// d_qoff[n_q + 1]) into the sorted anchor set ax / ay (oword: scratch).  Returns 1 with
-// nothing written where it does not apply (no anchors, or no word for the layout).
+// d_qoff[n_q + 1]) into the sorted anchor set ax / ay (oword: scratch; ay holds y's low word,
+// the span stays with the caller).  Returns 1 with nothing written where it does not apply (no
+// anchors, or no word for the layout).
 // hb: the set's group-head bitmap (head_bits_bytes(n); AnchorOut::head); ax32: x's low words.
 // d_stats (nullable, four zeroed counters): what the block sorts did -- segments and anchors
 // finished by their outlier path, segments and anchors that took the full sort.
 int grouped_anchor_sort(hymet_ctx *ctx, const uint64_t *word, int64_t n, const int64_t *d_qoff, int n_q, int rb, int pb,
-                        uint64_t yhi, int64_t max_qlen, uint64_t *oword, uint64_t *ax, uint64_t *ay, uint32_t *hb,
+                        int64_t max_qlen, uint64_t *oword, uint64_t *ax, uint32_t *ay, uint32_t *hb,
                         uint32_t *ax32, unsigned long long *d_stats = nullptr);
 // bytes of an anchor set's group-head bitmap: one bit per anchor, in whole 64-bit words (the
 // group kernels read two words per thread)

@@ -38,7 +38,7 @@ struct hymet_mm_result {
 namespace hymet {
 namespace mm {
 
-int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const int32_t *ids, const int64_t *cfirst,
+int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint32_t *ay, int span, const int32_t *ids, const int64_t *cfirst,
                    const uint64_t *cu, const int64_t *cboff,
                    const int64_t *qc, const int64_t *qb, const uint64_t *mini_pos, const int64_t *mp_off, const int64_t *qlen,
                    const uint32_t *name_hash, const int32_t *rep_len, const int64_t *ref_len, int n_q, const hymet_mm_opt *o,
@@ -323,7 +323,8 @@ struct AnchorParams {
     const uint64_t *ipos;
     int64_t n;
     int rb;                   // bits for rid
-    uint64_t *ax, *ay, *k1, *k2;
+    uint64_t *ax, *k1, *k2;
+    uint32_t *ay;             // y's low word (the span is idx->k for every minimizer)
     uint32_t *val;
     // mini_pos
     const int64_t *mp_pos;
@@ -359,7 +360,7 @@ __global__ void write_anchors_kernel(AnchorParams P) {
             y = (uint64_t)q_span << 32 | (uint32_t)(qlen - (int32_t)((q_pos >> 1) + 1 - q_span) - 1);
         }
         P.ax[a] = x;
-        P.ay[a] = y;
+        P.ay[a] = (uint32_t)y;
         P.k1[a] = (uint64_t)q << (1 + P.rb) | (uint64_t)rev << P.rb | rid;
         P.k2[a] = (uint64_t)rpos << 32 | (uint32_t)y;
         P.val[a] = (uint32_t)a;
@@ -446,8 +447,8 @@ __global__ __launch_bounds__(256) void write_anchor_keys_kernel(AnchorKeyParams 
 // sorted keys -> (x, y); runs of equal key (one query minimizer position hit by several
 // query minimizers) are ordered by y here: the lane at a run's start writes the run's y
 // values by insertion sort (runs are short and rare), the other lanes of the run skip y.
-__global__ void anchor_unpack_kernel(const uint64_t *key, const uint32_t *val, int64_t n, int rb, int pb, uint64_t yhi,
-                                     uint64_t *ax, uint64_t *ay) {
+__global__ void anchor_unpack_kernel(const uint64_t *key, const uint32_t *val, int64_t n, int rb, int pb, uint64_t *ax,
+                                     uint32_t *ay) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t k = key[i];
@@ -456,12 +457,12 @@ __global__ void anchor_unpack_kernel(const uint64_t *key, const uint32_t *val, i
     const bool prev_eq = i > 0 && key[i - 1] == k;
     const bool next_eq = i + 1 < n && key[i + 1] == k;
     if (!prev_eq && !next_eq) {
-        ay[i] = yhi << 32 | val[i];
+        ay[i] = val[i];
     } else if (!prev_eq) {
         int64_t e = i + 1;
         while (e + 1 < n && key[e + 1] == k) e++;
         for (int64_t a = i; a <= e; a++) {
-            const uint64_t v = yhi << 32 | val[a];
+            const uint32_t v = val[a];
             int64_t b = a;
             while (b > i && ay[b - 1] > v) {
                 ay[b] = ay[b - 1];
@@ -506,26 +507,27 @@ __global__ void mini_base_kernel(const uint64_t *my, const uint32_t *seed_n, con
 }
 
 // re-chain input: the chained anchors of flagged queries (query-major), with sort keys
-__global__ void rechain_gather_kernel(const uint64_t *bx, const uint64_t *by, const int64_t *qb, const uint32_t *qflag,
-                                      const int64_t *new_off, int n_q, int rb, uint64_t *x, uint64_t *y, uint64_t *k1,
+__global__ void rechain_gather_kernel(const uint64_t *bx, const uint32_t *by, const int64_t *qb, const uint32_t *qflag,
+                                      const int64_t *new_off, int n_q, int rb, uint64_t *x, uint32_t *y, uint64_t *k1,
                                       uint64_t *k2, uint32_t *val) {
     const int q = blockIdx.x;
     if (q >= n_q || !qflag[q]) return;
     const int64_t b0 = qb[q], b1 = qb[q + 1], o = new_off[q];
     for (int64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x) {
         const int64_t a = o + (i - b0);
-        const uint64_t ax = bx[i], ay = by[i];
+        const uint64_t ax = bx[i];
+        const uint32_t ay = by[i];
         x[a] = ax;
         y[a] = ay;
         k1[a] = (uint64_t)q << (1 + rb) | (ax >> 63) << rb | (ax << 1 >> 33);
-        k2[a] = (uint64_t)(uint32_t)ax << 32 | (uint32_t)ay;
+        k2[a] = (uint64_t)(uint32_t)ax << 32 | ay;
         val[a] = (uint32_t)a;
     }
 }
 
 // one thread per re-chain anchor (flat: a block per query left the long queries' blocks as
 // the tail); the block's first query by one binary search, each lane's by a short forward walk
-__global__ __launch_bounds__(256) void rechain_keys_kernel(const uint64_t *bx, const uint64_t *by, const int64_t *qb,
+__global__ __launch_bounds__(256) void rechain_keys_kernel(const uint64_t *bx, const uint32_t *by, const int64_t *qb,
                                                            const int64_t *new_off, int n_q, int64_t n, int rb, int pb,
                                                            int ybits, uint64_t *key, uint32_t *val) {
     __shared__ int s_q0;
@@ -540,10 +542,10 @@ __global__ __launch_bounds__(256) void rechain_keys_kernel(const uint64_t *bx, c
     const uint64_t ax = bx[i];
     const uint64_t k = (ax >> 63) << (rb + pb) | (ax << 1 >> 33) << pb | (uint32_t)ax;
     if (ybits) {  // words, as write_anchor_keys_kernel's
-        key[a] = k << ybits | (uint32_t)by[i];
+        key[a] = k << ybits | by[i];
     } else {
         key[a] = (uint64_t)q << (1 + rb + pb) | k;
-        val[a] = (uint32_t)by[i];
+        val[a] = by[i];
     }
 }
 
@@ -612,9 +614,9 @@ struct PhaseTrace {
     }
 };
 
-// sort raw anchors (x, y, k1 with k2 keys) into an AnchorSet
+// sort raw anchors (x, y's low word, k1 with k2 keys) into an AnchorSet
 static int sort_anchor_set(hymet_ctx *ctx, DevBuf &x, DevBuf &y, DevBuf &k1, DevBuf &k2, DevBuf &val, int64_t n,
-                           int key1_bits, AnchorSet &out) {
+                           int key1_bits, int yhi, AnchorSet &out) {
     DevBuf k2b, valb, k1g, k1b;
     HY_HIP(k2b.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(valb.alloc(4 * (size_t)n, ctx->stream));
@@ -629,10 +631,11 @@ static int sort_anchor_set(hymet_ctx *ctx, DevBuf &x, DevBuf &y, DevBuf &k1, Dev
     rc = sort_pairs(ctx, k1p, k1a, vv, vva, n, 0, key1_bits, "radix_sort_anchor_group");
     if (rc) return rc;
     HY_HIP(out.ax.alloc(8 * (size_t)n, ctx->stream));
-    HY_HIP(out.ay.alloc(8 * (size_t)n, ctx->stream));
+    HY_HIP(out.ay.alloc(4 * (size_t)n, ctx->stream));
     LAUNCH1(gather_kernel<uint64_t>, n, x.as<uint64_t>(), vv, out.ax.as<uint64_t>(), n);
-    LAUNCH1(gather_kernel<uint64_t>, n, y.as<uint64_t>(), vv, out.ay.as<uint64_t>(), n);
+    LAUNCH1(gather_kernel<uint32_t>, n, y.as<uint32_t>(), vv, out.ay.as<uint32_t>(), n);
     out.n = n;
+    out.span = yhi & 0xff;
     return HYMET_OK;
 }
 
@@ -643,10 +646,11 @@ static int sort_anchor_words(hymet_ctx *ctx, DevBuf &word, int64_t n, int rb, in
     DevBuf wb;
     HY_HIP(wb.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(out.ax.alloc(8 * (size_t)n, ctx->stream));
-    HY_HIP(out.ay.alloc(8 * (size_t)n, ctx->stream));
+    HY_HIP(out.ay.alloc(4 * (size_t)n, ctx->stream));
     HY_HIP(out.hb.alloc(head_bits_bytes(n), ctx->stream));
     HY_HIP(out.ax32.alloc(4 * (size_t)n, ctx->stream));
     out.n = n;
+    out.span = yhi & 0xff;
     // HYMET_ASORT_STATS=1: every batch's block-sort counts on stderr (a measuring aid: it
     // adds a stream synchronise per batch) -- segments and anchors finished by the outlier
     // path, segments and anchors that took the full sort
@@ -656,8 +660,8 @@ static int sort_anchor_words(hymet_ctx *ctx, DevBuf &word, int64_t n, int rb, in
         HY_HIP(sstat.alloc(32, ctx->stream));
         HY_HIP(hipMemsetAsync(sstat.p, 0, 32, ctx->stream));
     }
-    const int rc = grouped_anchor_sort(ctx, word.as<uint64_t>(), n, d_qoff, n_q, rb, pb, (uint64_t)yhi, max_qlen,
-                                       wb.as<uint64_t>(), out.ax.as<uint64_t>(), out.ay.as<uint64_t>(),
+    const int rc = grouped_anchor_sort(ctx, word.as<uint64_t>(), n, d_qoff, n_q, rb, pb, max_qlen,
+                                       wb.as<uint64_t>(), out.ax.as<uint64_t>(), out.ay.as<uint32_t>(),
                                        out.hb.as<uint32_t>(), out.ax32.as<uint32_t>(),
                                        log_stats ? sstat.as<unsigned long long>() : nullptr);
     if (rc == 1) return hymet::fail(HYMET_E_INTERNAL, "sort_anchor_words: anchor words emitted for a layout without one");
@@ -682,15 +686,16 @@ static int sort_anchor_keys(hymet_ctx *ctx, DevBuf &key, DevBuf &val, int64_t n,
     HY_HIP(kb.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(vb.alloc(4 * (size_t)n, ctx->stream));
     HY_HIP(out.ax.alloc(8 * (size_t)n, ctx->stream));
-    HY_HIP(out.ay.alloc(8 * (size_t)n, ctx->stream));
+    HY_HIP(out.ay.alloc(4 * (size_t)n, ctx->stream));
     out.n = n;
+    out.span = yhi & 0xff;
     uint64_t *kk = key.as<uint64_t>(), *kka = kb.as<uint64_t>();
     uint32_t *vv = val.as<uint32_t>(), *vva = vb.as<uint32_t>();
     int rc = sort_pairs<uint64_t, uint32_t>(ctx, kk, kka, vv, vva, n, 0, end_bit, "radix_sort_anchors");
     if (rc) return rc;
     {
-        ProfScope _ps(ctx, "mm_anchor_unpack", 28.0 * (double)n);  // key + value read, x + y write
-        LAUNCH1(anchor_unpack_kernel, n, kk, vv, n, rb, pb, (uint64_t)yhi, out.ax.as<uint64_t>(), out.ay.as<uint64_t>());
+        ProfScope _ps(ctx, "mm_anchor_unpack", 24.0 * (double)n);  // key + value read, x + y (4 B) write
+        LAUNCH1(anchor_unpack_kernel, n, kk, vv, n, rb, pb, out.ax.as<uint64_t>(), out.ay.as<uint32_t>());
     }
     return HYMET_OK;
 }
@@ -705,10 +710,11 @@ static int dump_anchors(hymet_ctx *ctx, const char *var, const AnchorSet &S, int
     dumped = true;
     hipStream_t st = ctx->stream;
     const int64_t nd = std::min<int64_t>(S.n, env_int("HYMET_DUMP_MAX", 1 << 24, 0, INT64_MAX));  // anchors to dump
-    std::vector<uint64_t> hx(nd), hy(nd);
+    std::vector<uint64_t> hx(nd);
+    std::vector<uint32_t> hy(nd);  // widened with the set's span on the way out
     std::vector<int64_t> qo(n_q + 1);
     HY_HIP(hipMemcpyAsync(hx.data(), S.ax.p, 8 * (size_t)nd, hipMemcpyDeviceToHost, st));
-    HY_HIP(hipMemcpyAsync(hy.data(), S.ay.p, 8 * (size_t)nd, hipMemcpyDeviceToHost, st));
+    HY_HIP(hipMemcpyAsync(hy.data(), S.ay.p, 4 * (size_t)nd, hipMemcpyDeviceToHost, st));
     HY_HIP(hipMemcpyAsync(qo.data(), S.d_off.p, 8 * (size_t)(n_q + 1), hipMemcpyDeviceToHost, st));
     HY_HIP(hipStreamSynchronize(st));
     if (FILE *fp = fopen(path, "wb")) {
@@ -721,7 +727,7 @@ static int dump_anchors(hymet_ctx *ctx, const char *var, const AnchorSet &S, int
             while (q < n_q && qo[q + 1] <= a) q++, qs = true;
             if (a && (qs || (hx[a] >> 32) != (hx[a - 1] >> 32))) gid++;
             buf.push_back(gid << 32 | (uint32_t)hx[a]);
-            buf.push_back(hy[a]);
+            buf.push_back((uint64_t)S.span << 32 | hy[a]);
             if (buf.size() >= (1u << 21)) fwrite(buf.data(), 8, buf.size(), fp), buf.clear();
         }
         fwrite(buf.data(), 8, buf.size(), fp);
@@ -1028,16 +1034,16 @@ static int first_pass_anchors(MapBatch &B, AnchorSet &S1) {
     }
     DevBuf x, y, k1, k2, val;
     HY_HIP(x.alloc(8 * (size_t)(A + 1), st));
-    HY_HIP(y.alloc(8 * (size_t)(A + 1), st));
+    HY_HIP(y.alloc(4 * (size_t)(A + 1), st));
     HY_HIP(k1.alloc(8 * (size_t)(A + 1), st));
     HY_HIP(k2.alloc(8 * (size_t)(A + 1), st));
     HY_HIP(val.alloc(4 * (size_t)(A + 1), st));
     AnchorParams P{mx.as<uint64_t>(), my.as<uint64_t>(), seed_n.as<uint32_t>(), a_pos.as<int64_t>(), qid.as<uint32_t>(),
-                   d_qlen.as<int64_t>(), idx->d_koff, idx->d_pos, M, B.rb, x.as<uint64_t>(), y.as<uint64_t>(),
-                   k1.as<uint64_t>(), k2.as<uint64_t>(), val.as<uint32_t>(), mp_pos.as<int64_t>(), B.mini_pos.as<uint64_t>()};
+                   d_qlen.as<int64_t>(), idx->d_koff, idx->d_pos, M, B.rb, x.as<uint64_t>(), k1.as<uint64_t>(),
+                   k2.as<uint64_t>(), y.as<uint32_t>(), val.as<uint32_t>(), mp_pos.as<int64_t>(), B.mini_pos.as<uint64_t>()};
     ProfScope _ps(ctx, "mm_anchors", (double)A * (8.0 + 36.0));  // position fetch + anchor/key writes
     LAUNCH1(write_anchors_kernel, M, P);
-    return sort_anchor_set(ctx, x, y, k1, k2, val, A, B.key1_bits, S1);
+    return sort_anchor_set(ctx, x, y, k1, k2, val, A, B.key1_bits, idx->k, S1);
 }
 
 // 7 long join, its anchor set: the chain anchors of the queries the first pass flagged
@@ -1069,22 +1075,22 @@ static int long_join_anchors(MapBatch &B, const AnchorSet &S1, const ChainSet &C
         DevBuf key, val;
         HY_HIP(key.alloc(8 * (size_t)(A2 + 1), st));
         if (!words) HY_HIP(val.alloc(4 * (size_t)(A2 + 1), st));
-        LAUNCH1(rechain_keys_kernel, A2, C1.bx.as<uint64_t>(), C1.by.as<uint64_t>(), C1.d_qb.as<int64_t>(),
+        LAUNCH1(rechain_keys_kernel, A2, C1.bx.as<uint64_t>(), C1.by.as<uint32_t>(), C1.d_qb.as<int64_t>(),
                 S2.d_off.as<int64_t>(), n_q, A2, B.rb, B.pb, words ? B.ybits : 0, key.as<uint64_t>(), val.as<uint32_t>());
         rc = words ? sort_anchor_words(ctx, key, A2, B.rb, B.pb, B.idx->k, S2.d_off.as<int64_t>(), n_q, B.max_qlen, S2)
                    : sort_anchor_keys(ctx, key, val, A2, B.key1_bits + B.pb, B.rb, B.pb, B.idx->k, S2);
     } else {
         DevBuf x, y, k1, k2, val;
         HY_HIP(x.alloc(8 * (size_t)(A2 + 1), st));
-        HY_HIP(y.alloc(8 * (size_t)(A2 + 1), st));
+        HY_HIP(y.alloc(4 * (size_t)(A2 + 1), st));
         HY_HIP(k1.alloc(8 * (size_t)(A2 + 1), st));
         HY_HIP(k2.alloc(8 * (size_t)(A2 + 1), st));
         HY_HIP(val.alloc(4 * (size_t)(A2 + 1), st));
         hipLaunchKernelGGL(rechain_gather_kernel, dim3((unsigned)n_q), dim3(256), 0, st, C1.bx.as<uint64_t>(),
-                           C1.by.as<uint64_t>(), C1.d_qb.as<int64_t>(), flag.as<uint32_t>(), S2.d_off.as<int64_t>(), n_q,
-                           B.rb, x.as<uint64_t>(), y.as<uint64_t>(), k1.as<uint64_t>(), k2.as<uint64_t>(), val.as<uint32_t>());
+                           C1.by.as<uint32_t>(), C1.d_qb.as<int64_t>(), flag.as<uint32_t>(), S2.d_off.as<int64_t>(), n_q,
+                           B.rb, x.as<uint64_t>(), y.as<uint32_t>(), k1.as<uint64_t>(), k2.as<uint64_t>(), val.as<uint32_t>());
         HY_CHECK_LAUNCH("rechain_gather_kernel");
-        rc = sort_anchor_set(ctx, x, y, k1, k2, val, A2, B.key1_bits, S2);
+        rc = sort_anchor_set(ctx, x, y, k1, k2, val, A2, B.key1_bits, S1.span, S2);
     }
     if (rc) return rc;
     static bool dumped = false;
@@ -1103,7 +1109,7 @@ static int run_regions(MapBatch &B, ChainSet &C, DevBuf &rg, DevBuf &nr, const u
     HY_HIP(cov.alloc(8 * (size_t)(NC + 1), st));
     HY_HIP(tmp.alloc(4 * (size_t)(NC + 1), st));
     HY_HIP(nr.alloc(4 * (size_t)B.n_q, st));
-    return launch_regions(B.ctx, C.ax, C.ay, C.ids.as<int32_t>(), C.cfirst.as<int64_t>(), C.cu.as<uint64_t>(),
+    return launch_regions(B.ctx, C.ax, C.ay, C.span, C.ids.as<int32_t>(), C.cfirst.as<int64_t>(), C.cu.as<uint64_t>(),
                           C.cboff.as<int64_t>(), C.d_qc.as<int64_t>(), C.d_qb.as<int64_t>(), B.mini_pos.as<uint64_t>(),
                           B.mp_off.as<int64_t>(), B.d_qlen.as<int64_t>(), B.d_hash, B.rep_len.as<int32_t>(), B.idx->d_len,
                           B.n_q, B.opt, B.idx->k, z.p, rg.as<hymet_mm_reg>(), wv.as<int32_t>(), cov.as<uint64_t>(),

@@ -59,7 +59,9 @@ __device__ void heap_sort(T *a, int64_t n, Less less) {
 }
 
 struct RegParams {
-    const uint64_t *ax, *ay;       // the chained anchor set
+    const uint64_t *ax;            // the chained anchor set
+    const uint32_t *ay;            // (y's low word; y = span << 32 | ay)
+    int span;
     const int32_t *ids;            // backtrack output (chains end -> start)
     const int64_t *cfirst;         // each chain's first slot in it
     const uint64_t *cu;            // score<<32 | count per chain
@@ -92,10 +94,9 @@ struct RegParams {
     int prim_regs;                 // set_parent primaries held in registers (64; HYMET_REG_PRIM in tests)
 };
 
-// (x0, y0): the chain's first anchor, (x1, y1): its last
-__device__ void set_coor(hymet_mm_reg *r, int32_t qlen, uint64_t x0, uint64_t y0, uint64_t x1, uint64_t y1, int32_t mlen,
-                         int32_t blen) {
-    const int32_t q_span = (int32_t)(y0 >> 32 & 0xff);
+// (x0, y0): the chain's first anchor, (x1, y1): its last (y's low words; q_span: the set's span)
+__device__ void set_coor(hymet_mm_reg *r, int32_t qlen, uint64_t x0, uint32_t y0, uint64_t x1, uint32_t y1, int32_t q_span,
+                         int32_t mlen, int32_t blen) {
     r->rev = (int32_t)(x0 >> 63);
     r->rid = (int32_t)(x0 << 1 >> 33);
     r->rs = (int32_t)x0 + 1 > q_span ? (int32_t)x0 + 1 - q_span : 0;
@@ -112,7 +113,9 @@ __device__ void set_coor(hymet_mm_reg *r, int32_t qlen, uint64_t x0, uint64_t y0
 }
 
 struct AnchorStatParams {
-    const uint64_t *ax, *ay, *cu;
+    const uint64_t *ax, *cu;
+    const uint32_t *ay;           // y's low word
+    int span;                     // y's high word, the set's constant
     const int32_t *ids;           // backtrack output (chains end -> start)
     const int64_t *cfirst;        // each chain's first slot in it
     const int64_t *cboff, *qb, *qlen, *mp_off;
@@ -140,9 +143,9 @@ struct AnchorStatParams {
 // chain order come from the adjacent lanes (a load only at a wave edge); then a segmented
 // wave reduction by chain and one atomic per chain piece in the wave.  c_mlen / c_blen
 // start at 0, c_fv at INT32_MAX (every anchor offers cnt).
-__device__ __forceinline__ int32_t mini_idx_at(const AnchorStatParams &P, int64_t q, int qlen, uint64_t ax, uint64_t ay) {
+__device__ __forceinline__ int32_t mini_idx_at(const AnchorStatParams &P, int64_t q, int qlen, uint64_t ax, uint32_t ay) {
     int32_t x = (int32_t)ay;
-    if (ax >> 63) x = qlen - 1 - (int32_t)ay + (int32_t)(ay >> 32 & 0xff) - 1;
+    if (ax >> 63) x = qlen - 1 - (int32_t)ay + P.span - 1;
     return (x >= 0 && x < qlen) ? mini_word_idx(P.mtab[(P.qbase[q] + x) >> 6], x) : -1;
 }
 
@@ -182,7 +185,8 @@ __global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams 
     int64_t c[K], q[K], f0[K];  // chain, query, slot of chain-order position 0 in ids
     bool act[K];
     int32_t cnt[K], j[K], qlen[K], cur[K];
-    uint64_t x[K], y[K];
+    uint64_t x[K];
+    uint32_t y[K];
     // a block inside one chain (long chains: most blocks) skips the searches and sums its
     // statistics over the block
     const bool one_chain = s_st[1] >= kStatSpan;
@@ -260,7 +264,7 @@ __global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams 
 #pragma unroll
     for (int k = 0; k < K; k++) {  // mini_idx_at, its table read unconditional
         int32_t xq = (int32_t)y[k];
-        if (x[k] >> 63) xq = qlen[k] - 1 - (int32_t)y[k] + (int32_t)(y[k] >> 32 & 0xff) - 1;
+        if (x[k] >> 63) xq = qlen[k] - 1 - (int32_t)y[k] + P.span - 1;
         const bool inq = xq >= 0 && xq < qlen[k];
         const int32_t xc = inq ? xq : 0;
         const int32_t v = mini_word_idx(P.mtab[(qb[k] + xc) >> 6], xc);
@@ -272,8 +276,8 @@ __global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams 
         // chain), else loaded
         const int32_t ci = (int32_t)c[k];
         const int32_t cprev = __shfl_up(ci, 1, 64), cnext = __shfl_down(ci, 1, 64);
-        uint64_t xp = __shfl_up(x[k], 1, 64), yp = __shfl_up(y[k], 1, 64);
-        uint64_t xn = __shfl_down(x[k], 1, 64), yn = __shfl_down(y[k], 1, 64);
+        uint64_t xp = __shfl_up(x[k], 1, 64), xn = __shfl_down(x[k], 1, 64);
+        uint32_t yp = __shfl_up(y[k], 1, 64), yn = __shfl_down(y[k], 1, 64);
         const int32_t cur_p = __shfl_up(cur[k], 1, 64), cur_n = __shfl_down(cur[k], 1, 64);
         int dm = 0, db = 0, fv = INT32_MAX;
         if (act[k]) {
@@ -287,7 +291,7 @@ __global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams 
                 const int64_t a = P.ids[f0[k] - j[k] - 1];
                 xn = P.ax[a], yn = P.ay[a];
             }
-            const int32_t span = (int32_t)(y[k] >> 32 & 0xff);
+            const int32_t span = P.span;
             if (j[k] == 0) {
                 dm = db = span;
             } else {  // hit.c mm_reg_set_coor
@@ -406,7 +410,7 @@ __device__ void regions_seq(const RegParams &P, int q) {
         const int64_t k = P.cboff[c0 + i] - b0;
         const uint64_t u = P.cu[c0 + i];
         const int64_t a = P.ids[P.cfirst[c0 + i] + (int32_t)u - 1];  // the chain's first anchor
-        const uint32_t h = (uint32_t)hash64((hash64(P.ax[a]) + hash64(P.ay[a])) ^ hash);
+        const uint32_t h = (uint32_t)hash64((hash64(P.ax[a]) + hash64((uint64_t)P.span << 32 | P.ay[a])) ^ hash);
         z[i].x = u ^ h;
         z[i].y = (uint64_t)k << 32 | (uint32_t)i;  // (mm_gen_regs: count; k is unique per chain, so
                                                    // the low word never orders -- the chain index instead)
@@ -433,7 +437,7 @@ __device__ void regions_seq(const RegParams &P, int q) {
         ri->mapq = 0;
         ri->pad = (int32_t)(c - c0);  // the region's chain, until mm_est_err (cleared in mm_set_mapq)
         const int64_t a0 = P.ids[P.cfirst[c] + ri->cnt - 1], a1 = P.ids[P.cfirst[c]];  // first, last anchor
-        set_coor(ri, qlen, P.ax[a0], P.ay[a0], P.ax[a1], P.ay[a1], P.c_mlen[c], P.c_blen[c]);
+        set_coor(ri, qlen, P.ax[a0], P.ay[a0], P.ax[a1], P.ay[a1], P.span, P.c_mlen[c], P.c_blen[c]);
     }
     // ---- mm_set_parent (mask_level, mask_len; no alignment: no dp_max branch)
     {
@@ -759,7 +763,7 @@ __device__ __forceinline__ void regions_wave(const RegParams &P, int q, unsigned
             const int64_t k = P.cboff[c0 + i] - b0;
             const uint64_t u = P.cu[c0 + i];
             const int64_t a = P.ids[P.cfirst[c0 + i] + (int32_t)u - 1];
-            const uint32_t h = (uint32_t)hash64((hash64(P.ax[a]) + hash64(P.ay[a])) ^ hash);
+            const uint32_t h = (uint32_t)hash64((hash64(P.ax[a]) + hash64((uint64_t)P.span << 32 | P.ay[a])) ^ hash);
             zz.x = u ^ h;
             zz.y = (uint64_t)k << 32 | (uint32_t)i;  // the chain index, not its count (as regions_seq)
         }
@@ -785,7 +789,7 @@ __device__ __forceinline__ void regions_wave(const RegParams &P, int q, unsigned
         ri.mapq = 0;
         ri.pad = (int32_t)(c - c0);  // the region's chain, until mm_est_err (cleared in mm_set_mapq)
         const int64_t a0 = P.ids[P.cfirst[c] + ri.cnt - 1], a1 = P.ids[P.cfirst[c]];
-        set_coor(&ri, qlen, P.ax[a0], P.ay[a0], P.ax[a1], P.ay[a1], P.c_mlen[c], P.c_blen[c]);
+        set_coor(&ri, qlen, P.ax[a0], P.ay[a0], P.ax[a1], P.ay[a1], P.span, P.c_mlen[c], P.c_blen[c]);
         r[i] = ri;
         slot[i] = make_int4(ri.qs, ri.qe, ri.score, ri.cnt);  // this lane's own sort slot
         aux[i] = make_int4(ri.rid | ri.rev << 31, ri.rs, ri.re, 0);
@@ -1151,7 +1155,7 @@ __global__ void chain_stats_init_kernel(int32_t *c_mlen, int32_t *c_blen, int32_
 
 }  // namespace
 
-int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const int32_t *ids, const int64_t *cfirst,
+int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint32_t *ay, int span, const int32_t *ids, const int64_t *cfirst,
                    const uint64_t *cu, const int64_t *cboff,
                    const int64_t *qc, const int64_t *qb, const uint64_t *mini_pos, const int64_t *mp_off, const int64_t *qlen,
                    const uint32_t *name_hash, const int32_t *rep_len, const int64_t *ref_len, int n_q, const hymet_mm_opt *o,
@@ -1165,9 +1169,9 @@ int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const
     int32_t *c_mlen = cst.as<int32_t>(), *c_blen = c_mlen + (NC + 1), *c_st = c_blen + (NC + 1), *c_last = c_st + (NC + 1),
             *c_fv = c_last + (NC + 1);
     {
-        // chain slot (4) + anchor x, y (16) + its minimizer-table read (4: 16 B per 64 bases) per chained anchor
-        ProfScope _ps(ctx, "mm_chain_stats", (double)NB * (4.0 + 16.0 + 4.0) + (double)NM * 8.0);
-        AnchorStatParams A{ax, ay, cu, ids, cfirst, cboff, qb, qlen, mp_off, mini_pos, NB, NC, n_q, cq,
+        // chain slot (4) + anchor x, y (8 + 4) + its minimizer-table read (4: 16 B per 64 bases) per chained anchor
+        ProfScope _ps(ctx, "mm_chain_stats", (double)NB * (4.0 + 12.0 + 4.0) + (double)NM * 8.0);
+        AnchorStatParams A{ax, cu, ay, span, ids, cfirst, cboff, qb, qlen, mp_off, mini_pos, NB, NC, n_q, cq,
                            c_mlen, c_blen, c_st, c_last, mtab, qbase, skip_q};
         if (NB > 0) {
             hipLaunchKernelGGL(chain_stats_init_kernel, dim3((unsigned)cdiv(NC + 1, 256)), dim3(256), 0, st, c_mlen, c_blen,
@@ -1188,7 +1192,7 @@ int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint64_t *ay, const
             HY_CHECK_LAUNCH("query_sumk_kernel");
         }
     }
-    RegParams P{ax, ay, ids, cfirst, cu, cboff, qc, qb, mini_pos, mp_off, qlen, name_hash, rep_len, ref_len, n_q, o->seed, k,
+    RegParams P{ax, ay, span, ids, cfirst, cu, cboff, qc, qb, mini_pos, mp_off, qlen, name_hash, rep_len, ref_len, n_q, o->seed, k,
                 o->mask_level, o->pri_ratio, o->mask_len, o->best_n, o->max_gap, o->min_chain_score, (U128 *)z, regs, w, cov,
                 tmp, n_regs, c_mlen, c_blen, c_st, c_last, c_fv, sumk, skip_q, kRegWave, kRegSmall, nullptr, 64};
     // tests / A-B: HYMET_REG_WAVE (chains above which a query takes the wave kernel),

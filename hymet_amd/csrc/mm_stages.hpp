@@ -61,9 +61,13 @@ inline int scan_flags(hymet_ctx *ctx, const uint32_t *flag, int64_t n, DevBuf &p
 // error with a small input.
 inline int64_t anchor_cap() { return env_int("HYMET_ANCHOR_CAP", INT32_MAX - 1, 1, INT32_MAX - 1); }
 
-// An anchor set sorted by (query, x, y): arrays + per-query offsets (device + host).
+// An anchor set sorted by (query, x, y): arrays + per-query offsets (device + host).  y is
+// span << 32 | query position, and the span is one value for the whole set (k, for every
+// minimizer of a non-HPC sketch): the array holds the low word alone.
 struct AnchorSet {
-    DevBuf ax, ay;
+    DevBuf ax;            // 8 B per anchor: rev << 63 | rid << 32 | target position
+    DevBuf ay;            // 4 B per anchor: y's low word
+    int span = 0;         // y's high word
     int64_t n = 0;
     DevBuf d_off;
     DevBuf hb;            // group-head bitmap (head_bits_bytes(n)): bit i where x >> 32 changes
@@ -77,8 +81,10 @@ struct AnchorSet {
 struct ChainSet {
     DevBuf cu, cboff;          // per chain: score<<32 | count; offset of its anchors in chain order
     DevBuf ids, cfirst;        // backtrack output (each chain end -> start) and each chain's first slot
-    const uint64_t *ax = nullptr, *ay = nullptr;  // the chained anchor set (alive as long as the chains)
-    DevBuf bx, by, bchain;     // a copy of the chained anchors in chain order (only for re-chain paths)
+    const uint64_t *ax = nullptr;  // the chained anchor set (alive as long as the chains)
+    const uint32_t *ay = nullptr;
+    int span = 0;
+    DevBuf bx, by, bchain;     // a copy of the chained anchors in chain order (only for re-chain paths; by: 4 B)
     DevBuf cq;                 // query of each chain
     int64_t n_anchor = 0, n_chain = 0;
     DevBuf d_qc, d_qb;  // n_q + 1 chain / chain-order anchor offsets per query

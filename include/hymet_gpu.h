@@ -368,10 +368,23 @@ int hymet_emit_paf(hymet_ctx *ctx, const hymet_paf_acc *acc, const uint8_t *d_qn
  * parity tests and kernel timing: n anchors (x, y as minimap2 packs them) of ONE query,
  * sorted by x; groups are runs of equal x>>32.  max_dist/bw are given as mg_lchain_rmq
  * receives them (first pass: max_gap, bw; long join: max_gap, bw_long).  Host arrays,
- * synchronous; h_p holds anchor indices or -1 (32-bit links on the device, widened on copy-out). */
+ * synchronous; h_p holds anchor indices or -1 (32-bit links on the device, widened on copy-out).
+ * The device holds y's low word per anchor and one span (y's high word) per set: the high
+ * words of h_y must all be equal (HYMET_E_ARG otherwise). */
 int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, int64_t n, int max_dist,
                       int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap,
                       float pen_skip, int32_t *h_f, int64_t *h_p);
+/* The long join's compaction alone (the stage inside hymet_mm_map that selects the re-chained
+ * queries' chain anchors out of the first-pass set), for parity tests: n anchors (x, y; the
+ * high words of h_y all equal) of n_q queries, query q's at [h_qoff[q], h_qoff[q+1]), the
+ * backtrack's marks h_mark and the per-query flags h_qflag.  An anchor is kept iff its mark is
+ * 2 and its query is flagged.  Returns the kept anchors in order (h_ox, h_oy: room for n), their
+ * count *n_kept and the head bitmap h_ohb (room for (n + 31) / 32 words; (*n_kept + 31) / 32
+ * written): bit i set where kept anchor i is the first or its x >> 32 differs from kept anchor
+ * i - 1's.  Host arrays, synchronous. */
+int hymet_mm_mark_compact(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, const int32_t *h_mark, int64_t n,
+                          const int64_t *h_qoff, const uint32_t *h_qflag, int32_t n_q, uint64_t *h_ox, uint64_t *h_oy,
+                          uint32_t *h_ohb, int64_t *n_kept);
 /* The grouped anchor sort alone (the stage inside hymet_mm_map that puts a batch's anchor
  * keys in minimap2's order), for parity tests: n keys (query | strand | target in rb bits |
  * target position in pb bits) with values y, query-major, query q's at [h_qoff[q],

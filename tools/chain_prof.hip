@@ -38,7 +38,8 @@ int main(int argc, char **argv) {
     const int bw = atoi(argv[2]);
     std::vector<uint64_t> hx(n), hy(n);
     for (int64_t i = 0; i < n; i++) hx[i] = a[2 * i], hy[i] = a[2 * i + 1];
-    uint64_t *dx, *dy;
+    uint64_t *dx;
+    uint32_t *dy;  // y's low words; the span (the dump's y >> 32, one value) goes in ChainParams
     int64_t *gs;
     int32_t *dp;
     int32_t *order, *cnt, *df, *dt;
@@ -46,7 +47,7 @@ int main(int argc, char **argv) {
     int4 *sum;
     const size_t ns = (size_t)(n >> 6) + (size_t)n / 2 + 4;
     CK(hipMalloc(&dx, 8 * n));
-    CK(hipMalloc(&dy, 8 * n));
+    CK(hipMalloc(&dy, 4 * n));
     CK(hipMalloc(&gs, 16));
     CK(hipMalloc(&dp, 4 * n));
     CK(hipMalloc(&order, 4));
@@ -63,7 +64,12 @@ int main(int argc, char **argv) {
         CK(hipMalloc(&dx32, 4 * n));
         CK(hipMemcpy(dx32, h32.data(), 4 * n, hipMemcpyHostToDevice));
     }
-    CK(hipMemcpy(dy, hy.data(), 8 * n, hipMemcpyHostToDevice));
+    const int32_t span = n > 0 ? (int32_t)(hy[0] >> 32 & 0xff) : 0;
+    {
+        std::vector<uint32_t> y32(n);
+        for (int64_t i = 0; i < n; i++) y32[i] = (uint32_t)hy[i];
+        CK(hipMemcpy(dy, y32.data(), 4 * n, hipMemcpyHostToDevice));
+    }
     // groups = runs of equal x >> 32, work list by size descending, group 0 holds anchor 0
     std::vector<int64_t> h_gs;
     for (int64_t i = 0; i < n; i++)
@@ -122,7 +128,7 @@ int main(int argc, char **argv) {
         CK(hipMemset(df, 0, 4 * n));
         CK(hipMemset(dp, 0xFF, 4 * n));
         CK(hipMemset(dt, 0, 4 * n));  // t arrives zeroed (overflow stamps are i + 1)
-        ChainParams P{dx32, dy, gs, qf, order, nwork, cnt, df, dp, dt, sum, max_dist, 1000, bw, 25, 100000, 0.12f, 0.0f, nullptr};
+        ChainParams P{dx32, dy, span, gs, qf, order, nwork, cnt, df, dp, dt, sum, max_dist, 1000, bw, 25, 100000, 0.12f, 0.0f, nullptr};
         hipEvent_t e0, e1;
         CK(hipEventCreate(&e0));
         CK(hipEventCreate(&e1));
