@@ -86,6 +86,7 @@ _SIGS = {
     "hymet_emit_tsv": (_i32, [_vp, _i32, _i32] + [_vp] * 14 + [_i64, _c.POINTER(_i64)]),
     "hymet_mm_chain_dp": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _c.c_float, _c.c_float, _vp, _vp]),
     "hymet_mm_mark_compact": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _c.POINTER(_i64)]),
+    "hymet_mm_stamp_scratch": (_i32, [_vp, _c.POINTER(_i64), _c.POINTER(_i64)]),
     "hymet_mm_anchor_sort": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _u64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "hymet_lca_ref_counts": (_i32, [_vp, _vp, _i64, _vp]),
     "hymet_lca": (_i32, [_vp, _i32, _i32] + [_vp] * 17),

@@ -35,6 +35,14 @@ struct hymet_ctx {
     // device counters that kernels leave zeroed (hymet::mm::publish_counters), so counting
     // kernels need no memset before them
     int32_t *dctr = nullptr;
+    // the chaining DP's "visited in this iteration" stamps (lchain.c's t[]), one word per anchor
+    // of the largest set chained so far (hymet::stamp_scratch).  Like dctr it is left zeroed:
+    // every word is zero whenever no chaining kernel of this context runs -- a group that
+    // stamped its range clears it before it ends -- so no call fills it but the one that grows
+    // it.  Released by hymet_scratch_trim and hymet_destroy.
+    int32_t *stamp = nullptr;
+    int64_t stamp_cap = 0;   // anchors
+    size_t stamp_cls = 0;    // its block's size class in the scratch cache
 };
 
 namespace hymet {
@@ -107,6 +115,10 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 hipError_t scratch_alloc(size_t bytes, hipStream_t stream, void **p, size_t *cls);
 void set_oom_hook(void (*hook)(void *), void *user);
 void scratch_free(void *p, hipStream_t stream, size_t cls);
+// the context's stamp scratch (hymet_ctx::stamp) with room for n anchors: grown, and zero-filled
+// on the context's stream, only when n exceeds its capacity
+hipError_t stamp_scratch(hymet_ctx *ctx, int64_t n, int32_t **out);
+void stamp_release(hymet_ctx *ctx);
 }  // namespace hymet
 
 #define HY_CHECK_LAUNCH(what)                                   \

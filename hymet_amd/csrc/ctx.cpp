@@ -145,6 +145,35 @@ int64_t scratch_cached() {
     return (int64_t)g_cached;
 }
 
+hipError_t stamp_scratch(hymet_ctx *ctx, int64_t n, int32_t **out) {
+    if (n > ctx->stamp_cap) {
+        // the old block goes back to the cache behind the kernels that stamped it (they left
+        // it zeroed, but a cached block is anyone's); the new one is zeroed here, once
+        stamp_release(ctx);
+        void *p = nullptr;
+        size_t cls = 0;
+        hipError_t e = scratch_alloc(4 * (size_t)n, ctx->stream, &p, &cls);
+        if (e != hipSuccess) return e;
+        e = hipMemsetAsync(p, 0, cls, ctx->stream);
+        if (e != hipSuccess) {
+            scratch_free(p, ctx->stream, cls);
+            return e;
+        }
+        ctx->stamp = (int32_t *)p;
+        ctx->stamp_cap = (int64_t)(cls / 4);
+        ctx->stamp_cls = cls;
+    }
+    *out = ctx->stamp;
+    return hipSuccess;
+}
+
+void stamp_release(hymet_ctx *ctx) {
+    if (ctx->stamp) scratch_free(ctx->stamp, ctx->stream, ctx->stamp_cls);
+    ctx->stamp = nullptr;
+    ctx->stamp_cap = 0;
+    ctx->stamp_cls = 0;
+}
+
 void scratch_stats(int64_t *out) {
     std::lock_guard<std::mutex> lk(g_cache_mu);
     for (int k = 0; k < 3; k++) out[k] = g_stats[k];
@@ -200,6 +229,7 @@ int hymet_destroy(hymet_ctx *ctx) {
     }
     if (ctx->mbox_h) (void)hipHostFree(ctx->mbox_h);
     if (ctx->dctr) (void)hipFree(ctx->dctr);
+    if (ctx->stamp) (void)hipFree(ctx->stamp);  // not to the cache: its stream goes with the context
     if (ctx->prof_dev) (void)hipFree(ctx->prof_dev);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -209,6 +239,10 @@ int hymet_destroy(hymet_ctx *ctx) {
 int hymet_set_stream(hymet_ctx *ctx, void *s) {
     HY_ARG(ctx != nullptr, "hymet_set_stream: null ctx");
     HY_HIP(hipSetDevice(ctx->device));
+    if (ctx->stamp) {  // the stamp scratch is cached per stream: it does not follow the context to another
+        HY_HIP(hipStreamSynchronize(ctx->stream));
+        hymet::stamp_release(ctx);
+    }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     ctx->stream = (hipStream_t)s;
     ctx->own_stream = false;
@@ -275,6 +309,7 @@ int hymet_scratch_trim(hymet_ctx *ctx, int64_t *freed_bytes) {
     HY_ARG(ctx != nullptr, "hymet_scratch_trim: null ctx");
     HY_HIP(hipSetDevice(ctx->device));
     HY_HIP(hipDeviceSynchronize());  // cached blocks of every stream of the device go back
+    hymet::stamp_release(ctx);       // and this context's stamp scratch with them (regrown, and zeroed, at the next chaining call)
     return hymet::scratch_trim(ctx->device, freed_bytes);
 }
 

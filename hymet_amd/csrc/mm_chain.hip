@@ -27,8 +27,8 @@
 //   * the inner window (x within rmq_inner_dist) is a (y, idx) sorted ring-deque in LDS (the
 //     krmq inner tree's in-order sequence; colinear inserts append, colinear erases pop the
 //     front); the walk's "visited in this iteration" stamps (lchain.c's t[]) go to t_global
-//     as i + 1 (the walk is rare on real anchors; t arrives zeroed and is re-zeroed after a
-//     group that stamped it).  A candidate of the
+//     as i + 1 (the walk is rare on real anchors; t_global is the context's stamp scratch,
+//     which arrives zeroed and is re-zeroed after a group that stamped it).  A candidate of the
 //     inner walk scores at most f_j + span_j, so when a monotone max-deque over the window
 //     says max(f_j + span_j) <= max_f the walk cannot change max_f/max_j and is skipped.
 //     Otherwise the walk is evaluated 64 candidates at a time: scores lane-parallel, the
@@ -156,7 +156,8 @@ struct ChainParams {
     int32_t *work_counter;
     int32_t *f;
     int32_t *p;               // predecessor, absolute in the anchor set (n < INT32_MAX, chain_set), -1: none
-    int32_t *t_global;        // overflow path only
+    int32_t *t_global;        // the inner walk's stamps (list walk and overflow walk), one word per anchor: the
+                              // context's stamp scratch (hymet_ctx::stamp), zero on entry and on exit
     int4 *sum;                // block summaries of every group (group g at ((g_start[g] >> 6) + g) * kGSumInts)
     int max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size;
     float pen_gap, pen_skip;
@@ -633,7 +634,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             return (int32_t)P.ay[g0 + jl];
         };
         int32_t i0 = 0, st = 0, st_in = 0;
-        bool t_used = false;  // the overflow walk stamped t_global
+        bool t_used = false;  // an inner walk stamped t_global
         auto sum_at = [&](int32_t b, int k) -> int4 {  // word k of block b's summary
             if ((i0 >> 6) - b <= kSumRing) return ssum[(b & (kSumRing - 1)) * kSumInts + k];
             return ld_l2(gsum + (int64_t)b * kGSumInts + k);
@@ -1517,7 +1518,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
                                 } else if (ld_l2(P.t_global + g0 + bjl) == i + 1) {
                                     if (++n_skip > P.max_chn_skip) break;
                                 }
-                                // stamp i + 1 (t arrives zeroed); every lane writes: program order
+                                // stamp i + 1 (t_global arrives zeroed); every lane writes: program order
                                 if (ej.p() >= 0) P.t_global[g0 + ej.p()] = i + 1;
                                 t_used = true;
                             }
@@ -1527,9 +1528,8 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             }
             CPROF(4);
             advance(i + 1);
-            // every lane stores the same values: later global loads by any lane see them.  t is
-            // cleared as each anchor is decided (the backtrack's marks start at 0; the walk's
-            // stamps only ever land on earlier anchors, and are cleared at the group's end)
+            // every lane stores the same values: later global loads by any lane see them (the
+            // walk's stamps only ever land on earlier anchors, and are cleared at the group's end)
             P.f[g0 + i] = max_f;
             P.p[g0 + i] = max_j < 0 ? -1 : (int32_t)(g0 + max_j);
             prev.x = xi, prev.y = yi, prev.f = max_f, prev.pw = (int32_t)((uint32_t)(max_j + 1) | (uint32_t)span_pw);
@@ -1540,7 +1540,7 @@ __global__ __launch_bounds__(64) HYMET_CHAIN_ATTR void chain_groups_kernel(Chain
             __builtin_amdgcn_wave_barrier();
             ++i;
         }
-        if (t_used) {  // hand the backtrack a zeroed t again
+        if (t_used) {  // the stamp scratch is left zeroed (hymet_ctx::stamp's invariant)
             __builtin_amdgcn_wave_barrier();
             for (int32_t j = lane; j < n; j += 64) P.t_global[g0 + j] = 0;
         }
@@ -1553,7 +1553,9 @@ struct BacktrackParams {
     const int64_t *g_start;
     const int32_t *f;
     const int32_t *p;
-    int32_t *t;                // zeroed by the caller
+    uint8_t *t;                // marks, one byte per anchor, zeroed by the caller.  Groups are disjoint anchor ranges
+                               // marked by one thread or one wave each, but neighbours share 32-bit words:
+                               // byte stores only, never a read-modify-write of a wider word
     const int32_t *z_cnt;      // per group: length of its (f, idx)-ascending z list
     const int32_t *z_idx;      // per group, from g_start[g]: anchor indices by (f, idx) ascending
     int32_t n_groups;
@@ -2183,12 +2185,12 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint32_t *ay, int span
     return HYMET_OK;
 }
 
-int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int32_t *p, int32_t *t,
+int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int32_t *p, uint8_t *t,
                      const int32_t *z_cnt, const int32_t *z_idx, int32_t n_groups, const int32_t *order, int32_t n_work,
                      int min_cnt, int min_sc, int max_drop, int32_t *chain_ids, uint64_t *chain_u, int64_t *chain_first,
                      int32_t *n_chains, int64_t n_anchors) {
     if (n_groups <= 0) return HYMET_OK;
-    // t arrives zeroed (chain_set's fill; a chaining group that stamped it re-zeroed it)
+    // t arrives zeroed (chain_set's fill)
     const int64_t long_min = env_int("HYMET_BT_LONG", kBtLong, 0, INT64_MAX);
     const bool prof = env_flag("HYMET_BT_PROF");
     DevBuf pbuf;
@@ -2200,8 +2202,8 @@ int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, c
                       long_min, (unsigned long long *)pbuf.p, chain_ids, chain_u, chain_first, n_chains};
     DevBuf cnt;
     HY_HIP(cnt.alloc(4 * (size_t)kBtCtrPad * (kBtStripes + 1), ctx->stream));  // [0] long groups, then the stripe counters
-    // z index + t probe + walked (p, f) + t mark + chain id write, 4 B each, per anchor
-    ProfScope _ps(ctx, "mm_backtrack", 24.0 * (double)n_anchors);
+    // z index + walked (p, f) + chain id write, 4 B each, + t probe + t mark, 1 B each, per anchor
+    ProfScope _ps(ctx, "mm_backtrack", 18.0 * (double)n_anchors);
     if (n_work > 0) {
         hipLaunchKernelGGL(bt_long_count_kernel, dim3(1), dim3(1), 0, ctx->stream, g_start, order, n_work, long_min,
                            cnt.as<int32_t>());

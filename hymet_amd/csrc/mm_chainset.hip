@@ -17,7 +17,7 @@ int launch_chain(hymet_ctx *ctx, const int32_t *ax, const uint32_t *ay, int span
                  const int32_t *order, int32_t n_work, int32_t *f, int32_t *p, int32_t *t_global, int max_dist,
                  int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap, float pen_skip,
                  int64_t n_anchors, int64_t n_groups);
-int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int32_t *p, int32_t *t,
+int launch_backtrack(hymet_ctx *ctx, const int64_t *g_start, const int32_t *f, const int32_t *p, uint8_t *t,
                      const int32_t *z_cnt, const int32_t *z_idx, int32_t n_groups, const int32_t *order, int32_t n_work,
                      int min_cnt, int min_sc, int max_drop, int32_t *chain_ids, uint64_t *chain_u, int64_t *chain_first,
                      int32_t *n_chains, int64_t n_anchors);
@@ -136,14 +136,18 @@ __global__ void max_group_kernel(const int64_t *g_start, const int32_t *order, i
     *out = best;
 }
 
-// groups of fewer than min_cnt anchors: f = 0, p = -1, t = 0 (the chaining kernels write f and
-// p of the anchors of every work group, so neither needs a pass over the set)
-__global__ void nonwork_fp_kernel(const int64_t *g_start, int32_t G, int min_cnt, int32_t *f, int32_t *p, int32_t *t) {
+// groups of fewer than min_cnt anchors: f = 0, p = -1, mark t = 0 (the chaining kernels write f
+// and p of the anchors of every work group, so neither needs a pass over the set).  t: byte
+// stores, a neighbouring group's marks share the word; null when the caller keeps no marks
+__global__ void nonwork_fp_kernel(const int64_t *g_start, int32_t G, int min_cnt, int32_t *f, int32_t *p, uint8_t *t) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
     const int64_t a0 = g_start[g], a1 = g_start[g + 1];
     if (a1 - a0 >= min_cnt) return;
-    for (int64_t a = a0; a < a1; a++) f[a] = 0, p[a] = -1, t[a] = 0;
+    for (int64_t a = a0; a < a1; a++) {
+        f[a] = 0, p[a] = -1;
+        if (t) t[a] = 0;
+    }
 }
 
 // also clears the per-group query-first flags and the z-order list counters
@@ -649,9 +653,9 @@ __global__ __launch_bounds__(256) void chain_copy_kernel(const uint64_t *cu, con
 
 // Long-join anchors: the first pass's chain anchors (t == 2 after the backtrack) of the
 // flagged queries.  Thread l of a 4096-anchor tile decides anchors [16 l, 16 l + 16) of the
-// tile (16-byte loads of t; the query of the first by a binary search over the query
-// offsets, then stepping over the few query starts inside the 16).
-__device__ __forceinline__ uint32_t keep_bits16(const int32_t *t, int64_t n, const uint32_t *qflag, const int64_t *qoff,
+// tile (their 16 byte marks in one 16-byte load; the query of the first by a binary search
+// over the query offsets, then stepping over the few query starts inside the 16).
+__device__ __forceinline__ uint32_t keep_bits16(const uint8_t *t, int64_t n, const uint32_t *qflag, const int64_t *qoff,
                                                 int n_q, int64_t e0) {
     if (e0 >= n) return 0u;
     int lo = 0, hi = n_q - 1;  // last q with qoff[q] <= e0
@@ -662,17 +666,13 @@ __device__ __forceinline__ uint32_t keep_bits16(const int32_t *t, int64_t n, con
     }
     int q = lo;
     int64_t qend = qoff[q + 1];
-    int32_t v[16];
+    uint32_t v[4] = {0, 0, 0, 0};  // mark u: byte u & 3 of v[u >> 2]
     if (e0 + 16 <= n) {
-        const int4 *p4 = reinterpret_cast<const int4 *>(t + e0);
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int4 w = p4[u];
-            v[4 * u] = w.x, v[4 * u + 1] = w.y, v[4 * u + 2] = w.z, v[4 * u + 3] = w.w;
-        }
+        const uint4 w = *reinterpret_cast<const uint4 *>(t + e0);  // e0 is a multiple of 16
+        v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
     } else {
 #pragma unroll
-        for (int u = 0; u < 16; u++) v[u] = e0 + u < n ? t[e0 + u] : 0;
+        for (int u = 0; u < 16; u++) v[u >> 2] |= (e0 + u < n ? (uint32_t)t[e0 + u] : 0u) << (8 * (u & 3));
     }
     uint32_t bits = 0, fl = qflag[q];
 #pragma unroll
@@ -682,14 +682,14 @@ __device__ __forceinline__ uint32_t keep_bits16(const int32_t *t, int64_t n, con
             qend = qoff[q + 1];
             fl = qflag[q];
         }
-        bits |= (uint32_t)(v[u] == 2 && fl != 0) << u;
+        bits |= (uint32_t)((v[u >> 2] >> (8 * (u & 3)) & 0xffu) == 2u && fl != 0) << u;
     }
     return bits;
 }
 
 // (also each tile's last kept anchor, or -1: the compaction's group heads compare a tile's
 // first kept anchor with the one before it)
-__global__ __launch_bounds__(256) void mark_count_kernel(const int32_t *t, int64_t n, const uint32_t *qflag,
+__global__ __launch_bounds__(256) void mark_count_kernel(const uint8_t *t, int64_t n, const uint32_t *qflag,
                                                          const int64_t *qoff, int n_q, uint32_t *cnt, int64_t *last_kept) {
     __shared__ uint32_t ws[4];
     __shared__ int64_t wl[4];
@@ -717,7 +717,7 @@ __global__ __launch_bounds__(256) void mark_count_kernel(const int32_t *t, int64
 // bitmap ohb (zeroed): the previous kept anchor is a lower lane of the same 64-anchor chunk
 // (shuffle), else the last kept one of an earlier chunk of the tile (LDS), else the last kept
 // anchor of an earlier tile (last_kept, from the count).
-__global__ __launch_bounds__(256) void mark_compact_kernel(const int32_t *t, int64_t n, const uint32_t *qflag,
+__global__ __launch_bounds__(256) void mark_compact_kernel(const uint8_t *t, int64_t n, const uint32_t *qflag,
                                                            const int64_t *qoff, int n_q, const int64_t *tile_off,
                                                            const int64_t *last_kept, const uint64_t *ax, const uint32_t *ay,
                                                            uint64_t *ox, uint32_t *oy, uint32_t *ohb, uint32_t *ox32) {
@@ -902,17 +902,20 @@ static int build_work_list(hymet_ctx *ctx, const Groups &Gr, int min_cnt, WorkLi
     return HYMET_OK;
 }
 
-// f / p of every anchor (t arrives zeroed): the chaining kernels write those of the work
-// groups; the anchors of groups of fewer than min_cnt anchors get f = 0, p = -1 from
-// nonwork_fp_kernel instead of memsets of all n
+// f / p of every anchor: the chaining kernels write those of the work groups; the anchors of
+// groups of fewer than min_cnt anchors get f = 0, p = -1 from nonwork_fp_kernel instead of
+// memsets of all n.  The walk's stamps go to the context's stamp scratch (zero before and
+// after); mark: the backtrack's byte marks (zeroed by the caller), or none
 static int chain_dp(hymet_ctx *ctx, const DpArgs &a, const AnchorSet &A, const Groups &Gr, const WorkList &W, DevBuf &f,
-                    DevBuf &p, DevBuf &t) {
+                    DevBuf &p, uint8_t *mark) {
     HY_HIP(f.alloc(4 * (size_t)A.n, ctx->stream));
     HY_HIP(p.alloc(4 * (size_t)A.n, ctx->stream));
+    int32_t *stamp = nullptr;
+    HY_HIP(stamp_scratch(ctx, A.n, &stamp));
     LAUNCH1(nonwork_fp_kernel, Gr.G, Gr.g_start.as<int64_t>(), (int32_t)Gr.G, a.min_cnt, f.as<int32_t>(), p.as<int32_t>(),
-            t.as<int32_t>());
+            mark);
     return launch_chain(ctx, A.ax32.as<int32_t>(), A.ay.as<uint32_t>(), A.span, Gr.g_start.as<int64_t>(), Gr.qfirst.as<uint8_t>(),
-                        W.order.as<int32_t>(), (int32_t)W.n_work, f.as<int32_t>(), p.as<int32_t>(), t.as<int32_t>(), a.max_dist,
+                        W.order.as<int32_t>(), (int32_t)W.n_work, f.as<int32_t>(), p.as<int32_t>(), stamp, a.max_dist,
                         a.max_dist_inner, a.bw, a.max_chn_skip, a.cap_rmq_size, a.pen_gap, a.pen_skip, A.n, Gr.G);
 }
 
@@ -987,7 +990,7 @@ static int backtrack(hymet_ctx *ctx, const hymet_mm_opt *opt, int bw, int64_t n,
     HY_HIP(B.u.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(B.first.alloc(8 * (size_t)n, ctx->stream));
     HY_HIP(B.n_chains.alloc(4 * (size_t)Gr.G, ctx->stream));
-    return launch_backtrack(ctx, Gr.g_start.as<int64_t>(), f.as<int32_t>(), p.as<int32_t>(), t.as<int32_t>(), Z.cnt.as<int32_t>(),
+    return launch_backtrack(ctx, Gr.g_start.as<int64_t>(), f.as<int32_t>(), p.as<int32_t>(), t.as<uint8_t>(), Z.cnt.as<int32_t>(),
                             Z.idx.as<int32_t>(), (int32_t)Gr.G, W.order.as<int32_t>(), (int32_t)W.n_work, opt->min_cnt,
                             opt->min_chain_score, bw, B.ids.as<int32_t>(), B.u.as<uint64_t>(), B.first.as<int64_t>(),
                             B.n_chains.as<int32_t>(), n);
@@ -1103,13 +1106,14 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
     Groups Gr;
     rc = build_groups(ctx, A, n_q, Gr);
     if (rc) return rc;
-    // t (lchain.c's stamps during the DP, the backtrack's marks after it) is cleared by a fill
-    // here, not by the chaining kernels as they decide each anchor: the extra store made the
-    // first-pass wave kernel ~3 % slower and the fill overlaps the other mapping stream
-    // (profiles/r06_tzero/)
+    // t, the backtrack's marks (one byte per anchor, + 16 for the long join's 16-byte loads), is
+    // cleared by a fill here, not by the chaining kernels as they decide each anchor: the extra
+    // store made the first-pass wave kernel ~3 % slower and the fill overlaps the other mapping
+    // stream (profiles/r06_tzero/).  lchain.c's stamps during the DP are not in t: they live in
+    // the context's stamp scratch (chain_dp)
     DevBuf t;
-    HY_HIP(t.alloc(4 * (size_t)n, ctx->stream));
-    HY_HIP(hipMemsetAsync(t.p, 0, 4 * (size_t)n, ctx->stream));
+    HY_HIP(t.alloc((size_t)n + 16, ctx->stream));
+    HY_HIP(hipMemsetAsync(t.p, 0, (size_t)n + 16, ctx->stream));
     WorkList W;
     rc = build_work_list(ctx, Gr, opt->min_cnt, W);
     if (rc) return rc;
@@ -1118,7 +1122,7 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
                 (long long)W.n_work, (long long)W.largest);
     DevBuf f, p;
     rc = chain_dp(ctx, DpArgs{opt->max_gap, opt->rmq_inner_dist, bw, opt->max_chain_skip, opt->rmq_size_cap, pen_gap, pen_skip,
-                              opt->min_cnt}, A, Gr, W, f, p, t);
+                              opt->min_cnt}, A, Gr, W, f, p, t.as<uint8_t>());
     if (rc) return rc;
     ZOrder Z;
     rc = z_order(ctx, opt->min_chain_score, f, n, Gr, W, Z);
@@ -1139,7 +1143,7 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
 
 // the anchors of S1 with mark == 2 in flagged queries, compacted in S1's order into S2
 // (expect: their count as the caller knows it, or -1)
-static int compact_marked(hymet_ctx *ctx, const AnchorSet &S1, const int32_t *mark, const uint32_t *flag, int n_q,
+static int compact_marked(hymet_ctx *ctx, const AnchorSet &S1, const uint8_t *mark, const uint32_t *flag, int n_q,
                           int64_t expect, AnchorSet &S2) {
     hipStream_t st = ctx->stream;
     const int64_t n1 = S1.n, nt = cdiv(n1, 4096);
@@ -1173,7 +1177,7 @@ static int compact_marked(hymet_ctx *ctx, const AnchorSet &S1, const int32_t *ma
 int marked_anchor_set(hymet_ctx *ctx, const AnchorSet &S1, const LeanJoin &lj, const uint32_t *flag, int n_q, int64_t A2,
                       AnchorSet &S2) {
     if (A2 != lj.n2) return hymet::fail(HYMET_E_INTERNAL, "hymet_mm_map: long-join anchor count mismatch");
-    return compact_marked(ctx, S1, lj.mark.as<int32_t>(), flag, n_q, A2, S2);
+    return compact_marked(ctx, S1, lj.mark.as<uint8_t>(), flag, n_q, A2, S2);
 }
 
 // a caller's 64-bit y values as the device holds them: the low words, and the span they share
@@ -1221,16 +1225,46 @@ extern "C" int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint
     WorkList W;
     rc = build_work_list(ctx, Gr, 1, W);
     if (rc) return rc;
-    DevBuf f, p, t;
-    HY_HIP(t.alloc(4 * (size_t)n, st));
-    HY_HIP(hipMemsetAsync(t.p, 0, 4 * (size_t)n, st));
-    rc = chain_dp(ctx, DpArgs{max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, pen_gap, pen_skip, 1}, A, Gr, W, f, p, t);
+    DevBuf f, p;  // (no marks: the stamps are the context's, as for every caller)
+    rc = chain_dp(ctx, DpArgs{max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, pen_gap, pen_skip, 1}, A, Gr, W, f, p,
+                  nullptr);
     if (rc) return rc;
     HY_HIP(hipMemcpyAsync(h_f, f.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     std::vector<int32_t> p32((size_t)n);  // the links are 32-bit on the device: widened for the caller
     HY_HIP(hipMemcpyAsync(p32.data(), p.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HY_HIP(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; i++) h_p[i] = p32[(size_t)i];
+    return HYMET_OK;
+}
+
+namespace {
+__global__ __launch_bounds__(256) void stamp_nonzero_kernel(const int32_t *t, int64_t n, unsigned long long *out) {
+    unsigned long long c = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) c += t[i] != 0;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+}  // namespace
+
+extern "C" int hymet_mm_stamp_scratch(hymet_ctx *ctx, int64_t *capacity, int64_t *nonzero) {
+    HY_ARG(ctx && capacity && nonzero, "hymet_mm_stamp_scratch: null argument");
+    HY_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    HY_HIP(hipStreamSynchronize(st));
+    *capacity = ctx->stamp_cap;
+    *nonzero = 0;
+    if (ctx->stamp_cap == 0) return HYMET_OK;
+    DevBuf cnt;
+    HY_HIP(cnt.alloc(8, st));
+    HY_HIP(hipMemsetAsync(cnt.p, 0, 8, st));
+    const int64_t nb = std::min<int64_t>(cdiv(ctx->stamp_cap, 256), (int64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(stamp_nonzero_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const int32_t *)ctx->stamp, ctx->stamp_cap,
+                       cnt.as<unsigned long long>());
+    HY_CHECK_LAUNCH("stamp_nonzero_kernel");
+    unsigned long long h = 0;
+    HY_HIP(hipMemcpyAsync(&h, cnt.p, 8, hipMemcpyDeviceToHost, st));
+    HY_HIP(hipStreamSynchronize(st));
+    *nonzero = (int64_t)h;
     return HYMET_OK;
 }
 
@@ -1253,14 +1287,18 @@ extern "C" int hymet_mm_mark_compact(hymet_ctx *ctx, const uint64_t *h_x, const 
     HY_HIP(S1.ax.alloc(8 * (size_t)n, st));
     HY_HIP(S1.ay.alloc(4 * (size_t)n, st));
     HY_HIP(S1.d_off.alloc(8 * (size_t)(n_q + 1), st));
-    HY_HIP(mark.alloc(4 * (size_t)n + 16, st));
+    // the caller's int32 marks as the device holds them: bytes, narrowed so that only 2 stays 2
+    // (a stale stamp such as 258 must not truncate into a mark)
+    std::vector<uint8_t> m8((size_t)n);
+    for (int64_t i = 0; i < n; i++) m8[(size_t)i] = h_mark[i] == 2 ? 2 : (h_mark[i] != 0);
+    HY_HIP(mark.alloc((size_t)n + 16, st));
     HY_HIP(flag.alloc(4 * (size_t)n_q, st));
     HY_HIP(hipMemcpyAsync(S1.ax.p, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, st));
     HY_HIP(hipMemcpyAsync(S1.ay.p, y32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
     HY_HIP(hipMemcpyAsync(S1.d_off.p, h_qoff, 8 * (size_t)(n_q + 1), hipMemcpyHostToDevice, st));
-    HY_HIP(hipMemcpyAsync(mark.p, h_mark, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    HY_HIP(hipMemcpyAsync(mark.p, m8.data(), (size_t)n, hipMemcpyHostToDevice, st));
     HY_HIP(hipMemcpyAsync(flag.p, h_qflag, 4 * (size_t)n_q, hipMemcpyHostToDevice, st));
-    rc = compact_marked(ctx, S1, mark.as<int32_t>(), flag.as<uint32_t>(), n_q, -1, S2);
+    rc = compact_marked(ctx, S1, mark.as<uint8_t>(), flag.as<uint32_t>(), n_q, -1, S2);
     if (rc) {
         HY_HIP(hipStreamSynchronize(st));  // the uploads read the caller's arrays
         return rc;

@@ -99,7 +99,8 @@ struct LeanJoin {
     float rescue_ratio;
     bool mark_only;
     DevBuf flag;                 // per query: re-chained
-    DevBuf mark;                 // mark_only: per anchor of the set (+16 bytes for 16-byte loads)
+    DevBuf mark;                 // mark_only: the backtrack's marks, one byte per anchor of the set (+16 bytes
+                                 // for 16-byte loads): 2 = in a kept chain
     DevBuf qb2;                  // mark_only: n_q + 1 offsets of the re-chained queries' chain anchors
     int64_t n2 = 0;
 };

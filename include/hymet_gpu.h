@@ -57,7 +57,8 @@ int hymet_prof_names(hymet_ctx *ctx, char *buf, int64_t cap);
  * (best fit up to twice the request) and capped at HYMET_SCRATCH_CAP_GB (default 160) of
  * cached blocks.  trim synchronises the
  * device and returns every cached block of the device to HIP (e.g. before torch
- * allocates large tensors); cached reports the bytes held. */
+ * allocates large tensors), and with them this context's chaining stamp scratch
+ * (hymet_mm_stamp_scratch; regrown at the next chaining call); cached reports the bytes held. */
 int hymet_scratch_trim(hymet_ctx *ctx, int64_t *freed_bytes);
 int hymet_scratch_cached(hymet_ctx *ctx, int64_t *bytes);
 /* Allocates `bytes` of scratch on the context's stream and returns them to the cache at once
@@ -370,7 +371,8 @@ int hymet_emit_paf(hymet_ctx *ctx, const hymet_paf_acc *acc, const uint8_t *d_qn
  * receives them (first pass: max_gap, bw; long join: max_gap, bw_long).  Host arrays,
  * synchronous; h_p holds anchor indices or -1 (32-bit links on the device, widened on copy-out).
  * The device holds y's low word per anchor and one span (y's high word) per set: the high
- * words of h_y must all be equal (HYMET_E_ARG otherwise). */
+ * words of h_y must all be equal (HYMET_E_ARG otherwise).  The DP's stamps (lchain.c's t[])
+ * are the context's stamp scratch, as for hymet_mm_map. */
 int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, int64_t n, int max_dist,
                       int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap,
                       float pen_skip, int32_t *h_f, int64_t *h_p);
@@ -381,10 +383,17 @@ int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, 
  * 2 and its query is flagged.  Returns the kept anchors in order (h_ox, h_oy: room for n), their
  * count *n_kept and the head bitmap h_ohb (room for (n + 31) / 32 words; (*n_kept + 31) / 32
  * written): bit i set where kept anchor i is the first or its x >> 32 differs from kept anchor
- * i - 1's.  Host arrays, synchronous. */
+ * i - 1's.  Host arrays, synchronous.  The device holds one byte per mark: h_mark is narrowed on
+ * upload as m == 2 ? 2 : (m != 0), so a stale value such as 258 is no mark. */
 int hymet_mm_mark_compact(hymet_ctx *ctx, const uint64_t *h_x, const uint64_t *h_y, const int32_t *h_mark, int64_t n,
                           const int64_t *h_qoff, const uint32_t *h_qflag, int32_t n_q, uint64_t *h_ox, uint64_t *h_oy,
                           uint32_t *h_ohb, int64_t *n_kept);
+/* Debug: the context's chaining stamp scratch -- one int32 per anchor of the largest set the
+ * context has chained (4 B x that set), zero whenever no chaining kernel of the context runs,
+ * zero-filled only when it grows.  Synchronises the stream; *capacity in anchors (0 before the
+ * first chaining call and after hymet_scratch_trim), *nonzero the words that are not zero
+ * (counted on the device; 0 unless the invariant is broken). */
+int hymet_mm_stamp_scratch(hymet_ctx *ctx, int64_t *capacity, int64_t *nonzero);
 /* The grouped anchor sort alone (the stage inside hymet_mm_map that puts a batch's anchor
  * keys in minimap2's order), for parity tests: n keys (query | strand | target in rb bits |
  * target position in pb bits) with values y, query-major, query q's at [h_qoff[q],
