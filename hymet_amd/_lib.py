@@ -59,6 +59,9 @@ _SIGS = {
     "hymet_mash_dist_tile": (_i32, [_i32]),
     "hymet_mash_dist_tune": (_i32, [_i32, _i32]),
     "hymet_mash_dist_select": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _c.POINTER(_i64)]),
+    "hymet_mash_dist_tri": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "hymet_mash_link": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "hymet_mash_labels": (_i32, [_vp, _vp, _i64, _vp]),
     "hymet_mm_sketch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _c.POINTER(_i64)]),
     "hymet_mm_index_build": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(_vp)]),
     "hymet_mm_index_destroy": (_i32, [_vp]),

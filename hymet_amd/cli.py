@@ -31,6 +31,11 @@
            sketch, not a stage of the reference workflow)
     python -m hymet_amd.cli mash-screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE...
         == mash screen (the rows on stdout, in sketch order; -w: winner-take-all)
+    python -m hymet_amd.cli derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [-i] [-l] INPUT...
+        single-linkage clusters of the INPUT sketches under a distance threshold, one
+        representative per cluster, optionally the reduced .msh (no Mash command does this)
+    python -m hymet_amd.cli triangle [-i] [-l] INPUT...
+        == mash triangle (the lower-triangular distance matrix of the INPUT sketches)
 
 The thin wrappers under scripts/ call these, so run_hymet_cami.sh / main.pl can use them
 in place of the reference stage scripts unchanged.  All device work goes through
@@ -494,6 +499,179 @@ def cmd_dist(argv: Sequence[str]) -> int:
     return 0
 
 
+# ------------------------------------------------------------------ derep / triangle
+DEREP_USAGE = "usage: derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [-i] [-l] INPUT..."
+TRIANGLE_USAGE = "usage: triangle [-i] [-l] INPUT..."
+
+
+def derep_args(argv: Sequence[str]):
+    """Returns the parsed namespace, or None after printing the usage line (unknown flag, no
+    INPUT, -d outside [0, 1), an unknown -r rule)."""
+    class _Parser(argparse.ArgumentParser):
+        def error(self, message):
+            raise ValueError(message)
+
+    p = _Parser(prog="derep", add_help=False, allow_abbrev=False)
+    p.add_argument("-d", type=float, default=0.05, dest="max_dist")
+    p.add_argument("-r", default="longest", dest="rule")
+    p.add_argument("-o", dest="out")
+    p.add_argument("-k", type=int, default=21, dest="k")
+    p.add_argument("-s", type=int, default=1000, dest="s")
+    p.add_argument("-S", type=int, default=42, dest="seed")
+    p.add_argument("-i", action="store_true", dest="individual")
+    p.add_argument("-l", action="store_true", dest="lists")
+    p.add_argument("-h", action="store_true", dest="help")
+    p.add_argument("files", nargs="*")
+    try:
+        a = p.parse_args(list(argv))
+        if a.help:
+            print(cmd_derep.__doc__, file=sys.stderr)
+            raise ValueError("")
+        if not 0.0 <= a.max_dist < 1.0:
+            raise ValueError(f"-d {a.max_dist:g}: the distance threshold must be in [0, 1)")
+        if a.rule not in ("longest", "first"):
+            raise ValueError(f"-r {a.rule}: expected longest or first")
+        if not a.files:
+            raise ValueError("no INPUT")
+    except ValueError as e:
+        if str(e):
+            print(f"derep: {e}", file=sys.stderr)
+        print(DEREP_USAGE, file=sys.stderr)
+        return None
+    return a
+
+
+def triangle_args(argv: Sequence[str]):
+    """Returns the parsed namespace, or None after printing the usage line (unknown flag, no INPUT)."""
+    class _Parser(argparse.ArgumentParser):
+        def error(self, message):
+            raise ValueError(message)
+
+    p = _Parser(prog="triangle", add_help=False, allow_abbrev=False)
+    p.set_defaults(k=21, s=1000, seed=42)      # cmd_sketch's defaults, for FASTA INPUTs
+    p.add_argument("-i", action="store_true", dest="individual")
+    p.add_argument("-l", action="store_true", dest="lists")
+    p.add_argument("-h", action="store_true", dest="help")
+    p.add_argument("files", nargs="*")
+    try:
+        a = p.parse_args(list(argv))
+        if a.help:
+            print(cmd_triangle.__doc__, file=sys.stderr)
+            raise ValueError("")
+        if not a.files:
+            raise ValueError("no INPUT")
+    except ValueError as e:
+        if str(e):
+            print(f"triangle: {e}", file=sys.stderr)
+        print(TRIANGLE_USAGE, file=sys.stderr)
+        return None
+    return a
+
+
+def _load_inputs(gpu, inputs: Sequence[str], a):
+    """The INPUTs of derep / triangle as one sketch DB: a path ending in .msh is loaded, any other
+    is FASTA and sketched on the GPU with the parameters of the first .msh INPUT if there is one,
+    else with -k / -s / -S.  ValueError when two inputs do not go together."""
+    from . import mashdist as md
+    from . import sketch as sk
+    from .msh import load_db
+    loaded = {p: load_db(p) for p in inputs if p.endswith(".msh")}
+    first = next(iter(loaded.values()), None)
+    if first is not None:
+        md.check_compatible(first, first)
+        par = dict(k=first.k, seed=first.seed, s=first.sketch_size, preserve_case=first.preserve_case)
+    else:
+        par = dict(k=a.k, seed=a.seed, s=a.s, preserve_case=False)
+    dbs, fasta = [], []
+
+    def flush():      # consecutive FASTA inputs are sketched in one call
+        if fasta:
+            dbs.append(sk.sketch_files(gpu, list(fasta), individual=a.individual, **par))
+            fasta.clear()
+
+    for p in inputs:
+        if p in loaded:
+            flush()
+            dbs.append(loaded[p])
+        else:
+            fasta.append(p)
+    flush()
+    for d in dbs:
+        md.check_compatible(dbs[0], d)
+    return md.concat_dbs(dbs)
+
+
+def cmd_derep(argv: Sequence[str]) -> int:
+    """derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [-i] [-l] INPUT...:
+    single-linkage clusters of all INPUT sketches under the Mash distance D, computed on the GPU
+    (each pair once, the clusters formed in device memory); one row per sketch on stdout in input
+    order (member, representative, cluster index, cluster size) and a summary line on stderr.
+      -d  sketches within distance D share a cluster, 0 <= D < 1 (0.05)
+      -r  a cluster's representative: its longest genome (longest) or its first member (first)
+      -o  write PREFIX.msh holding the representatives only (the suffix is not doubled)
+      -i  one sketch per sequence of a FASTA INPUT      -l  INPUTs list paths
+      -k -s -S  k-mer size, sketch size and seed for FASTA INPUTs when no INPUT is a .msh
+                (21, 1000, 42); otherwise the first .msh INPUT's parameters are used
+    An INPUT ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU."""
+    a = derep_args(argv)
+    if a is None:
+        return 2
+    from . import derep as dr
+    from ._lib import Gpu
+    from .msh import write_msh
+    inputs = expand_lists(a.files) if a.lists else list(a.files)
+    if not inputs:
+        print("derep: no INPUT", file=sys.stderr)
+        print(DEREP_USAGE, file=sys.stderr)
+        return 2
+    gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
+    try:
+        db = _load_inputs(gpu, inputs, a)
+    except ValueError as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        return 1
+    if db.n_refs == 0:
+        print("ERROR: no sequences to sketch.", file=sys.stderr)
+        return 1
+    res = dr.cluster(gpu, db, a.max_dist)
+    reps = dr.representatives(res.labels, db.lengths, a.rule)
+    sys.stdout.write("".join(l + "\n" for l in dr.format_rows(db, res.labels, reps)))
+    print(f"derep: {db.n_refs} sketches, {res.n_links} links, {len(reps)} clusters", file=sys.stderr)
+    if a.out:
+        out = a.out if a.out.endswith(".msh") else a.out + ".msh"
+        print(f"Writing to {out}...", file=sys.stderr)
+        write_msh(dr.subset_db(db, reps), out)
+    return 0
+
+
+def cmd_triangle(argv: Sequence[str]) -> int:
+    """triangle [-i] [-l] INPUT...: the lower-triangular distance matrix of all INPUT sketches,
+    computed on the GPU: a first line with the number of sketches, then per sketch its name and
+    the distance to every earlier one.
+      -i  one sketch per sequence of a FASTA INPUT      -l  INPUTs list paths
+    An INPUT ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU with
+    the first .msh INPUT's parameters, or k = 21, s = 1000, seed 42 when there is none."""
+    a = triangle_args(argv)
+    if a is None:
+        return 2
+    from . import derep as dr
+    from ._lib import Gpu
+    inputs = expand_lists(a.files) if a.lists else list(a.files)
+    if not inputs:
+        print("triangle: no INPUT", file=sys.stderr)
+        print(TRIANGLE_USAGE, file=sys.stderr)
+        return 2
+    gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
+    try:
+        db = _load_inputs(gpu, inputs, a)
+    except ValueError as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        return 1
+    for line in dr.triangle_lines(gpu, db):
+        sys.stdout.write(line + "\n")
+    return 0
+
+
 # ------------------------------------------------------------------ mash-screen (mash screen)
 MASH_SCREEN_USAGE = "usage: mash-screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE..."
 
@@ -590,6 +768,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return cmd_dist(rest)
     if cmd == "mash-screen":
         return cmd_mash_screen(rest)
+    if cmd == "derep":
+        return cmd_derep(rest)
+    if cmd == "triangle":
+        return cmd_triangle(rest)
     print(f"unknown subcommand {cmd!r}", file=sys.stderr)
     return 2
 

@@ -28,6 +28,12 @@
 //   select_count / select_write: per row of the dense block, the references whose common
 //                reaches min_common[denom], in reference order: count, hymet_scan_u32's scan,
 //                write (ballot ranks inside a row: the order is the reference order).
+//   dist_tiled<true> / dist_tri_global: one DB against itself, the pairs r < q only (the lower
+//                triangle; hymet_mash_dist_tri).  A workgroup clips its references to those below
+//                its tile's last query and a wave skips a pair with r >= q.
+//   link       : the same filter over the r < q entries of a dense block, each passing pair united
+//                in a union-find over the sketches (hymet_mash_link; the rules stand at uf_find);
+//                labels: every sketch's root, the smallest index of its component.
 #include "mm_common.hpp"
 
 #include <algorithm>
@@ -91,6 +97,10 @@ __device__ __forceinline__ uint32_t wave_pair(PA A, int la, PB B, int lb, int s)
 }
 
 // grid: n_tiles * n_chunks blocks; block b = (tile b / n_chunks, reference chunk b % n_chunks)
+// TRI: references and queries are one DB and only the pairs r < q are computed and written.  The
+// tiles are taken last first: a tile's work grows with its first query, and the longest blocks
+// then start first and the short ones fill the tail.
+template <bool TRI>
 __global__ __launch_bounds__(kThreads) void dist_tiled_kernel(const uint64_t *__restrict__ rh,
                                                               const int64_t *__restrict__ roff, int64_t n_ref,
                                                               const uint64_t *__restrict__ qh,
@@ -102,10 +112,13 @@ __global__ __launch_bounds__(kThreads) void dist_tiled_kernel(const uint64_t *__
     uint64_t *Q = reinterpret_cast<uint64_t *>(smem + kLdsHdr);  // tq rows of s
     uint64_t *R = Q + (size_t)tq * s;                            // the staged reference
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t tile = blockIdx.x / n_chunks, ch = blockIdx.x % n_chunks;
+    const int64_t n_tiles = gridDim.x / n_chunks;
+    const int64_t tile = TRI ? n_tiles - 1 - blockIdx.x / n_chunks : blockIdx.x / n_chunks, ch = blockIdx.x % n_chunks;
     const int64_t q0 = q_begin + tile * tq;
     const int nq = (int)min((int64_t)tq, q_end - q0);
-    const int64_t r0 = ch * chunk, r1 = min(r0 + chunk, n_ref);
+    // TRI: the references below the tile's last query
+    const int64_t r0 = ch * chunk, r1 = min(r0 + chunk, TRI ? min(n_ref, q0 + nq - 1) : n_ref);
+    if (TRI && r0 >= r1) return;  // workgroup-uniform, before the first barrier
     for (int t = 0; t < nq; t++) {
         const int64_t b = qoff[q0 + t];
         const int len = (int)min((int64_t)s, qoff[q0 + t + 1] - b);
@@ -141,6 +154,7 @@ __global__ __launch_bounds__(kThreads) void dist_tiled_kernel(const uint64_t *__
         __syncthreads();  // the reference (and, the first time, the query tile) is staged
         if (r + 1 < r1) prefetch(r + 1);
         for (int t = wave; t < nq; t += kWaves) {
+            if (TRI && r >= q0 + t) continue;  // wave-uniform
             const uint32_t v = wave_pair(R, la, Q + (size_t)t * s, qlen[t], s);
             if (lane == 0) out[(size_t)(q0 - q_begin + t) * (size_t)n_ref + (size_t)r] = v;
         }
@@ -162,7 +176,9 @@ __global__ __launch_bounds__(kThreads) void dist_global_kernel(const uint64_t *_
     if ((threadIdx.x & 63) == 0) out[p] = v;
 }
 
-__device__ __forceinline__ bool select_pass(uint32_t v, const uint16_t *__restrict__ minc, int s) {
+// PT: pointer type, so that a table staged in LDS is read with LDS instructions
+template <typename PT>
+__device__ __forceinline__ bool select_pass(uint32_t v, PT minc, int s) {
     const uint32_t denom = v & 0xffffu;
     return denom <= (uint32_t)s && (v >> 16) >= (uint32_t)minc[denom];
 }
@@ -217,6 +233,135 @@ __global__ __launch_bounds__(kThreads) void select_write_kernel(const uint32_t *
     }
 }
 
+// one wave per entry of the rows x n block; the waves of the entries r >= q leave at once
+__global__ __launch_bounds__(kThreads) void dist_tri_global_kernel(const uint64_t *__restrict__ h,
+                                                                   const int64_t *__restrict__ off, int64_t n,
+                                                                   int64_t q_begin, int64_t n_pairs, int s,
+                                                                   uint32_t *__restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (p >= n_pairs) return;  // wave-uniform
+    const int64_t q = q_begin + p / n, r = p % n;
+    if (r >= q) return;  // wave-uniform
+    const int64_t rb = off[r], qb = off[q];
+    const int la = (int)min((int64_t)s, off[r + 1] - rb), lb = (int)min((int64_t)s, off[q + 1] - qb);
+    const uint32_t v = wave_pair(h + rb, la, h + qb, lb, s);
+    if ((threadIdx.x & 63) == 0) out[p] = v;
+}
+
+// ---- union-find over the sketches of one DB (hymet_mash_link, hymet_mash_labels)
+// Invariant: 0 <= parent[x] <= x; a root has parent[x] == x.  The only write that makes a root a
+// non-root is the CAS in uf_unite, which stores a smaller index; path shortening stores a smaller
+// ancestor (atomicMin).  So parent[x] only ever falls, through members of x's component, and a
+// component's root is its smallest member whatever order the atomics land in.
+// Every access to parent inside a launch is a relaxed agent-scope atomic (performed past the
+// XCD-private L2s, as scan.hip argues for its hand-off), but nothing rests on a load being fresh:
+//   * a stale parent[x] is an earlier value of the word, hence still an ancestor of x;
+//   * only the CAS decides a link: it succeeds only while hi is a root, and then lo < hi lies in
+//     another component (a root is the smallest member of its own); when it fails, the value it
+//     returned is hi's parent and the union goes on from there, the word is not read again;
+//   * two walks that end in the same index prove one component, for good: links are never removed.
+// uf_find follows only values v with 0 <= v < x, so it ends after at most x steps on any array
+// contents; any other value != x stops the walk and sets the error word (reported by
+// hymet_mash_labels).  The labels run in a launch of their own, after every link.
+__device__ __forceinline__ int32_t uf_ld(int32_t *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root above x as far as this thread sees it; -1 after a parent outside [0, x]
+__device__ __forceinline__ int32_t uf_find(int32_t *__restrict__ parent, int32_t x, int32_t *__restrict__ err) {
+    int32_t p = uf_ld(parent + x);
+    for (;;) {
+        if (p == x) return x;
+        if (p < 0 || p > x) {
+            __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return -1;
+        }
+        const int32_t g = uf_ld(parent + p);  // p < x
+        // shorten: x's grandparent, an ancestor below its parent (a root or a bad g: nothing stored)
+        if (g >= 0 && g < p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = g;
+    }
+}
+
+__device__ __forceinline__ void uf_unite(int32_t *__restrict__ parent, int32_t a, int32_t b,
+                                         int32_t *__restrict__ err) {
+    a = uf_find(parent, a, err);
+    b = uf_find(parent, b, err);
+    while (a >= 0 && b >= 0 && a != b) {
+        const int32_t hi = max(a, b), lo = min(a, b);
+        int32_t seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        // hi was linked by another thread: seen is its parent.  lo need not be a root any more;
+        // the next CAS is on the larger of the two again and decides the same way.
+        if (seen < 0 || seen > hi) {
+            __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        a = uf_find(parent, seen, err);
+        b = lo;
+    }
+}
+
+// Workgroup w takes the rows w, w + gridDim.x, ... of the block; row `row` is sketch q = q_begin +
+// row and only its entries r < q are read: 16-byte loads between the row's first and last
+// 16-byte boundary, single entries before and after.  The table is staged in LDS once.
+__global__ __launch_bounds__(kThreads) void link_kernel(const uint32_t *__restrict__ blk, int64_t n_rows, int64_t n,
+                                                        int64_t q_begin, const uint16_t *__restrict__ minc, int s,
+                                                        int32_t *__restrict__ parent,
+                                                        unsigned long long *__restrict__ n_links,
+                                                        int32_t *__restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ unsigned long long ws[kWaves];
+    uint16_t *tab = reinterpret_cast<uint16_t *>(smem);
+    for (int e = threadIdx.x; e <= s; e += kThreads) tab[e] = minc[e];
+    __syncthreads();
+    unsigned long long c = 0;
+    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        const int32_t q = (int32_t)(q_begin + row);
+        const uint32_t *p = blk + (size_t)row * (size_t)n;
+        const int64_t lim = q;  // q < n
+        const int64_t head = min(lim, (int64_t)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
+        const int64_t nvec = (lim - head) >> 2;
+        auto entry = [&](int64_t r, uint32_t v) {
+            if (select_pass(v, tab, s)) {
+                c++;
+                uf_unite(parent, q, (int32_t)r, err);
+            }
+        };
+        if ((int64_t)threadIdx.x < head) entry(threadIdx.x, p[threadIdx.x]);
+        const uint4 *pv = reinterpret_cast<const uint4 *>(p + head);
+        for (int64_t i = threadIdx.x; i < nvec; i += kThreads) {
+            const uint4 v = pv[i];
+            const int64_t r = head + 4 * i;
+            entry(r, v.x);
+            entry(r + 1, v.y);
+            entry(r + 2, v.z);
+            entry(r + 3, v.w);
+        }
+        const int64_t tail = head + 4 * nvec + threadIdx.x;  // fewer than 4 entries are left
+        if (tail < lim) entry(tail, p[tail]);
+    }
+    // the passing pairs of this workgroup: one integer atomic, so the total does not depend on order
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < kWaves; w++) t += ws[w];
+        if (t) atomicAdd(n_links, t);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void labels_kernel(int32_t *__restrict__ parent, int64_t n,
+                                                          int32_t *__restrict__ label, int32_t *__restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) label[i] = uf_find(parent, (int32_t)i, err);
+}
+
 // path 0: tiled where the tile fits, 1: always the plain kernel; tq 0: the default tile
 struct DistCfg {
     int path = 0, tq = 0;
@@ -241,9 +386,12 @@ int tile_for(int s) {
     return tq >= 2 ? tq : 0;
 }
 
-// offsets [0, n] of a device CSR: non-decreasing, inside [0, n_hashes]
-int check_offsets(hymet_ctx *ctx, const int64_t *d_off, int64_t n, int64_t n_hashes, const char *what) {
-    std::vector<int64_t> off((size_t)n + 1);
+// offsets [0, n] of a device CSR: non-decreasing, inside [0, n_hashes]; keep: the host copy
+int check_offsets(hymet_ctx *ctx, const int64_t *d_off, int64_t n, int64_t n_hashes, const char *what,
+                  std::vector<int64_t> *keep = nullptr) {
+    std::vector<int64_t> mine;
+    std::vector<int64_t> &off = keep ? *keep : mine;
+    off.resize((size_t)n + 1);
     HY_HIP(hipMemcpyAsync(off.data(), d_off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
     HY_HIP(hipStreamSynchronize(ctx->stream));
     HY_ARG(off[0] >= 0, std::string("hymet_mash_dist: ") + what + " offsets start below 0");
@@ -307,12 +455,114 @@ int hymet_mash_dist(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t n_ref_
     HY_ARG(n_tiles < (1ll << 31) / n_chunks, "hymet_mash_dist: too many tiles in one call");
     const size_t lds = (size_t)kLdsHdr + 8 * (size_t)s * (size_t)(tq + 1);
     if (lds > 64 * 1024)
-        HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_tiled_kernel),
+        HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_tiled_kernel<false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hymet::ProfScope _ps(ctx, "mash_dist", 8.0 * n_ref_hashes * (double)n_tiles + 4.0 * (double)n_pairs);
-    hipLaunchKernelGGL(dist_tiled_kernel, dim3((unsigned)(n_tiles * n_chunks)), dim3(kThreads), lds, st, d_ref_hashes,
+    hipLaunchKernelGGL(dist_tiled_kernel<false>, dim3((unsigned)(n_tiles * n_chunks)), dim3(kThreads), lds, st, d_ref_hashes,
                        d_ref_off, n_ref, d_qry_hashes, d_qry_off, q_begin, q_end, (int)s, tq, n_chunks, chunk, d_out);
     HY_CHECK_LAUNCH("dist_tiled_kernel");
+    return HYMET_OK;
+}
+
+int hymet_mash_dist_tri(hymet_ctx *ctx, const uint64_t *d_hashes, int64_t n_hashes, const int64_t *d_off, int64_t n,
+                        int64_t q_begin, int64_t q_end, int32_t s, uint32_t *d_out) {
+    HY_ARG(ctx, "hymet_mash_dist_tri: null context");
+    HY_ARG(s >= 1 && s <= kMaxS, "hymet_mash_dist_tri: sketch size must be in 1.." + std::to_string(kMaxS));
+    HY_ARG(n >= 0 && n < (1ll << 31) && n_hashes >= 0, "hymet_mash_dist_tri: count out of range");
+    HY_ARG(q_begin >= 0 && q_begin <= q_end && q_end <= n, "hymet_mash_dist_tri: row range outside [0, n]");
+    HY_ARG(d_off, "hymet_mash_dist_tri: null offsets");
+    HY_ARG(n_hashes == 0 || d_hashes, "hymet_mash_dist_tri: null hashes");
+    HY_HIP(hipSetDevice(ctx->device));
+    std::vector<int64_t> off;
+    const int rc = check_offsets(ctx, d_off, n, n_hashes, "sketch", &off);
+    if (rc) return rc;
+    const int64_t rows = q_end - q_begin;
+    if (rows == 0 || q_end <= 1) return HYMET_OK;  // row 0 has no earlier sketch
+    HY_ARG(d_out, "hymet_mash_dist_tri: null output");
+    const int64_t n_pairs = rows * n;  // below 2^62
+    const double written = 0.5 * ((double)q_end * (double)(q_end - 1) - (double)q_begin * (double)(q_begin - 1));
+    hipStream_t st = ctx->stream;
+    const int tq = tile_for(s);
+    if (tq == 0) {
+        const int64_t nb = hymet::cdiv(n_pairs, kWaves);
+        HY_ARG(nb < (1ll << 31), "hymet_mash_dist_tri: more than 2^33 entries in one call");
+        double read = 0.0;  // both lists of every written pair
+        if (ctx->prof)
+            for (int64_t q = std::max<int64_t>(q_begin, 1); q < q_end; q++)
+                read += 8.0 * ((double)std::min<int64_t>(s, off[q + 1] - off[q]) * (double)q);
+        hymet::ProfScope _ps(ctx, "mash_dist_tri", 2.0 * read + 4.0 * written);
+        hipLaunchKernelGGL(dist_tri_global_kernel, dim3((unsigned)nb), dim3(kThreads), 0, st, d_hashes, d_off, n, q_begin,
+                           n_pairs, (int)s, d_out);
+        HY_CHECK_LAUNCH("dist_tri_global_kernel");
+        return HYMET_OK;
+    }
+    const int64_t n_tiles = hymet::cdiv(rows, tq);
+    // the chunks are cut over the references below the call's last query, sized as hymet_mash_dist's
+    const int64_t n_below = q_end - 1;
+    int64_t n_chunks =
+        std::max<int64_t>(1, std::min(hymet::cdiv((int64_t)ctx->n_cu * 8, n_tiles), hymet::cdiv(n_below, 16)));
+    const int64_t chunk = hymet::cdiv(n_below, n_chunks);
+    n_chunks = hymet::cdiv(n_below, chunk);
+    HY_ARG(n_tiles < (1ll << 31) / n_chunks, "hymet_mash_dist_tri: too many tiles in one call");
+    const size_t lds = (size_t)kLdsHdr + 8 * (size_t)s * (size_t)(tq + 1);
+    if (lds > 64 * 1024)
+        HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_tiled_kernel<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    double staged = 0.0;  // reference hashes staged per tile, after the clip to the tile's last query
+    if (ctx->prof) {
+        std::vector<double> below((size_t)q_end, 0.0);  // below[x]: hashes read of the sketches [0, x)
+        for (int64_t r = 0; r + 1 < q_end; r++) below[r + 1] = below[r] + (double)std::min<int64_t>(s, off[r + 1] - off[r]);
+        for (int64_t t = 0; t < n_tiles; t++) staged += below[std::min(q_end, q_begin + (t + 1) * tq) - 1];
+    }
+    hymet::ProfScope _ps(ctx, "mash_dist_tri", 8.0 * staged + 4.0 * written);
+    hipLaunchKernelGGL(dist_tiled_kernel<true>, dim3((unsigned)(n_tiles * n_chunks)), dim3(kThreads), lds, st, d_hashes,
+                       d_off, n, d_hashes, d_off, q_begin, q_end, (int)s, tq, n_chunks, chunk, d_out);
+    HY_CHECK_LAUNCH("dist_tiled_kernel<tri>");
+    return HYMET_OK;
+}
+
+int hymet_mash_link(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n, int64_t q_begin,
+                    const uint16_t *d_min_common, int32_t s, int32_t *d_parent, uint64_t *d_n_links) {
+    HY_ARG(ctx, "hymet_mash_link: null context");
+    HY_ARG(s >= 1 && s <= kMaxS, "hymet_mash_link: sketch size must be in 1.." + std::to_string(kMaxS));
+    HY_ARG(n >= 0 && n < (1ll << 31), "hymet_mash_link: n outside [0, 2^31)");
+    HY_ARG(n_rows >= 0 && q_begin >= 0 && q_begin <= n && n_rows <= n - q_begin, "hymet_mash_link: rows outside [0, n]");
+    HY_ARG(d_min_common && d_n_links, "hymet_mash_link: null argument");
+    HY_HIP(hipSetDevice(ctx->device));
+    if (n_rows == 0 || q_begin + n_rows <= 1) return HYMET_OK;
+    HY_ARG(d_block && d_parent, "hymet_mash_link: null argument");
+    HY_ARG((reinterpret_cast<uintptr_t>(d_block) & 3) == 0, "hymet_mash_link: block not 4-byte aligned");
+    const double tri =
+        0.5 * ((double)(q_begin + n_rows) * (double)(q_begin + n_rows - 1) - (double)q_begin * (double)(q_begin - 1));
+    const int64_t nb = std::min<int64_t>(n_rows, (int64_t)ctx->n_cu * 8);
+    hymet::ProfScope _ps(ctx, "mash_link", 4.0 * tri);
+    hipLaunchKernelGGL(link_kernel, dim3((unsigned)nb), dim3(kThreads), 2 * ((size_t)s + 1), ctx->stream, d_block, n_rows, n,
+                       q_begin, d_min_common, (int)s, d_parent, reinterpret_cast<unsigned long long *>(d_n_links),
+                       ctx->dctr + hymet::mm::kCtrUfErr);
+    HY_CHECK_LAUNCH("link_kernel");
+    return HYMET_OK;
+}
+
+int hymet_mash_labels(hymet_ctx *ctx, int32_t *d_parent, int64_t n, int32_t *d_label) {
+    HY_ARG(ctx, "hymet_mash_labels: null context");
+    HY_ARG(n >= 0 && n < (1ll << 31), "hymet_mash_labels: n outside [0, 2^31)");
+    HY_ARG(n == 0 || (d_parent && d_label), "hymet_mash_labels: null argument");
+    HY_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int32_t *err = ctx->dctr + hymet::mm::kCtrUfErr;
+    if (n > 0) {
+        hymet::ProfScope _ps(ctx, "mash_labels", 8.0 * (double)n);
+        hipLaunchKernelGGL(labels_kernel, dim3((unsigned)hymet::cdiv(n, kThreads)), dim3(kThreads), 0, st, d_parent, n,
+                           d_label, err);
+        HY_CHECK_LAUNCH("labels_kernel");
+    }
+    int32_t bad = 0;
+    HY_HIP(hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
+    HY_HIP(hipStreamSynchronize(st));
+    if (bad) {
+        HY_HIP(hipMemsetAsync(err, 0, 4, st));  // left zeroed for the next clustering
+        return hymet::fail(HYMET_E_ARG, "hymet_mash_labels: a parent outside [0, x] was met");
+    }
     return HYMET_OK;
 }
 

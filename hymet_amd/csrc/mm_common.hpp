@@ -119,6 +119,9 @@ enum : int { kMbScan = 0, kMbGmax = 1, kMbZBig = 2, kMbZBigTotal = 3, kMbFlag = 
              kMbGroups = 20, kMbGClass = 24 };
 // self-clearing device counters (hymet_ctx::dctr): counters at [base, base + n), ticket at base + n
 enum : int { kCtrQClass = 0, kCtrGroups = 16, kCtrGClass = 24, kCtrScan = 40, kCtrMaxScan = 41, kCtrRegBig = 42, kCtrRegBig2 = 44 };
+// the union-find's error word (mash_dist.hip): set by a link or labels kernel that met a parent
+// outside [0, x], read and zeroed again by hymet_mash_labels
+enum : int { kCtrUfErr = 48 };
 
 // Called by every thread of every block after the block's last update of cnt[0, n): the last
 // block to arrive stores the totals into the mailbox words mail[0, n) and zeroes the counters

@@ -270,6 +270,32 @@ int hymet_mash_dist_tune(int path, int tq);
 int hymet_mash_dist_select(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n_ref,
                            const uint16_t *d_min_common, int32_t s, int64_t *d_row_off, int32_t *d_ref_idx,
                            uint32_t *d_val, int64_t cap, int64_t *total);
+/* One DB against itself, the lower triangle only: for the rows q in [q_begin, q_end) it writes
+ * d_out[(q - q_begin) * n + r] = common << 16 | denom for every r < q and nothing else (the
+ * entries r >= q keep what they held).  The pair routine, the argument checks (the offsets are
+ * copied to the host, which synchronises the stream), the tile size and therefore
+ * HYMET_DIST_PATH, HYMET_DIST_TQ and hymet_mash_dist_tune are those of hymet_mash_dist; every
+ * written entry equals hymet_mash_dist's of the DB with itself.  n < 2^31. */
+int hymet_mash_dist_tri(hymet_ctx *ctx, const uint64_t *d_hashes, int64_t n_hashes, const int64_t *d_off, int64_t n,
+                        int64_t q_begin, int64_t q_end, int32_t s, uint32_t *d_out);
+/* Single-linkage clustering of the n sketches of one DB: hymet_mash_dist_select's filter fused
+ * with a union-find.  d_block holds n_rows rows of n entries (as hymet_mash_dist_tri or
+ * hymet_mash_dist of the DB with itself writes them); row `row` is sketch q = q_begin + row,
+ * q_begin + n_rows <= n.  Every entry r < q with common >= d_min_common[denom] (and denom <= s)
+ * unites q and r in d_parent (int32[n], which the caller initialises to parent[i] = i before the
+ * first call) and adds 1 to *d_n_links (a uint64 in device memory, which the caller zeroes; one
+ * integer atomic per workgroup: the total is deterministic).  Entries r >= q are never read.
+ * Throughout, 0 <= parent[x] <= x, and a component's root is its smallest member.  A parent
+ * outside [0, x] met on the way sets an error word in the context, which hymet_mash_labels
+ * reports.  Queued on the context's stream; several calls over row blocks of one DB give the
+ * same components as one call.  n < 2^31, s in 1..hymet_sketch_max_size(). */
+int hymet_mash_link(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n, int64_t q_begin,
+                    const uint16_t *d_min_common, int32_t s, int32_t *d_parent, uint64_t *d_n_links);
+/* After the links: d_label[i] = the root of i, the smallest index of i's component (d_parent's
+ * paths are shortened on the way; its components stay).  Synchronises, and returns HYMET_E_ARG
+ * when a link kernel since the last call, or this call's kernel, met a parent outside [0, x]
+ * (the labels are then not to be used); the error word is cleared. */
+int hymet_mash_labels(hymet_ctx *ctx, int32_t *d_parent, int64_t n, int32_t *d_label);
 
 /* --------------------------------------------------- minimizer index (minimap2 -d)
  * Replaces `minimap2 -I2g -d reference.mmi combined_genomes.fasta` (scripts/minimap2.sh:12):
