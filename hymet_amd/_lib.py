@@ -62,6 +62,9 @@ _SIGS = {
     "hymet_mash_dist_tri": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "hymet_mash_link": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
     "hymet_mash_labels": (_i32, [_vp, _vp, _i64, _vp]),
+    "hymet_mash_dist_sparse": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _i32,
+                                      _i64, _vp, _vp, _vp, _i64, _c.POINTER(_i64), _vp]),
+    "hymet_mash_link_edges": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "hymet_mm_sketch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _c.POINTER(_i64)]),
     "hymet_mm_index_build": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(_vp)]),
     "hymet_mm_index_destroy": (_i32, [_vp]),
@@ -95,8 +98,13 @@ _SIGS = {
     "hymet_lca": (_i32, [_vp, _i32, _i32] + [_vp] * 17),
 }
 
+class SparseCounters(_c.Structure):
+    """hymet_sparse_counters: what one hymet_mash_dist_sparse call did."""
+    _fields_ = [("postings", _i64), ("emitted", _i64), ("candidates", _i64)]
+
+
 _lib = None
-_oom_hook = None   # kept referenced: the library holds the function pointer
+_oom_hook = None  # kept referenced: the library holds the function pointer
 
 
 def _release_torch_cache(_user):

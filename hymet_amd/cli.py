@@ -407,7 +407,7 @@ def cmd_sketch(argv: Sequence[str]) -> int:
 
 
 # ------------------------------------------------------------------ dist (mash dist)
-DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [-i] [-l] REF.msh QUERY..."
+DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [--sparse] [-i] [-l] REF.msh QUERY..."
 
 
 def dist_args(argv: Sequence[str]):
@@ -418,9 +418,10 @@ def dist_args(argv: Sequence[str]):
             raise ValueError(message)
 
     p = _Parser(prog="dist", add_help=False, allow_abbrev=False)
-    p.add_argument("-d", type=float, default=1.0, dest="max_dist")
+    p.add_argument("-d", type=float, default=None, dest="max_dist")
     p.add_argument("-v", type=float, default=1.0, dest="max_p")
     p.add_argument("-t", action="store_true", dest="table")
+    p.add_argument("--sparse", action="store_true", dest="sparse")
     p.add_argument("-i", action="store_true", dest="individual")
     p.add_argument("-l", action="store_true", dest="lists")
     p.add_argument("-h", action="store_true", dest="help")
@@ -434,6 +435,14 @@ def dist_args(argv: Sequence[str]):
             raise ValueError("no REF.msh")
         if len(a.files) < 2:
             raise ValueError("no QUERY")
+        if a.sparse and a.table:
+            raise ValueError("--sparse does not go with -t: the table holds every pair")
+        if a.sparse and a.max_dist is None:
+            raise ValueError("--sparse needs a distance threshold: give -d D with D < 1")
+        if a.sparse and not a.max_dist < 1.0:
+            raise ValueError(f"--sparse with -d {a.max_dist:g}: the distance threshold must be below 1")
+        if a.max_dist is None:
+            a.max_dist = 1.0
     except ValueError as e:
         if str(e):
             print(f"dist: {e}", file=sys.stderr)
@@ -444,12 +453,13 @@ def dist_args(argv: Sequence[str]):
 
 
 def cmd_dist(argv: Sequence[str]) -> int:
-    """mash dist [-d D] [-v P] [-t] [-i] [-l] REF.msh QUERY...: the distance of every QUERY
+    """mash dist [-d D] [-v P] [-t] [--sparse] [-i] [-l] REF.msh QUERY...: the distance of every QUERY
     sketch to every sketch of REF.msh, computed on the GPU; one row per pair on stdout
     (reference, query, distance, p-value, shared/compared hashes), query-major.
       -d  keep pairs with distance <= D (1)     -v  keep pairs with p-value <= P (1)
       -t  table output (ignores -d and -v)      -l  QUERYs list paths
       -i  one query per sequence of a FASTA QUERY
+      --sparse  with -d D, D < 1: visit only the pairs that share a hash (the same rows)
     A QUERY ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU with
     REF.msh's k-mer size, seed, sketch size and case rule."""
     a = dist_args(argv)
@@ -494,13 +504,13 @@ def cmd_dist(argv: Sequence[str]) -> int:
         denom = np.concatenate([p[3] for p in parts]) if parts else np.zeros(0, np.int32)
         sys.stdout.write("".join(l + "\n" for l in md.format_table(ref, qry, common, denom)))
         return 0
-    for qi, ri, common, denom in md.dist_blocks(gpu, ref, qry, a.max_dist, block_bytes=1 << 26):
+    for qi, ri, common, denom in md.dist_blocks(gpu, ref, qry, a.max_dist, block_bytes=1 << 26, sparse=a.sparse):
         sys.stdout.write("".join(l + "\n" for l in md.format_lines(ref, qry, qi, ri, common, denom, a.max_dist, a.max_p)))
     return 0
 
 
 # ------------------------------------------------------------------ derep / triangle
-DEREP_USAGE = "usage: derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [-i] [-l] INPUT..."
+DEREP_USAGE = "usage: derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [--sparse] [-i] [-l] INPUT..."
 TRIANGLE_USAGE = "usage: triangle [-i] [-l] INPUT..."
 
 
@@ -518,6 +528,7 @@ def derep_args(argv: Sequence[str]):
     p.add_argument("-k", type=int, default=21, dest="k")
     p.add_argument("-s", type=int, default=1000, dest="s")
     p.add_argument("-S", type=int, default=42, dest="seed")
+    p.add_argument("--sparse", action="store_true", dest="sparse")
     p.add_argument("-i", action="store_true", dest="individual")
     p.add_argument("-l", action="store_true", dest="lists")
     p.add_argument("-h", action="store_true", dest="help")
@@ -602,7 +613,7 @@ def _load_inputs(gpu, inputs: Sequence[str], a):
 
 
 def cmd_derep(argv: Sequence[str]) -> int:
-    """derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [-i] [-l] INPUT...:
+    """derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [--sparse] [-i] [-l] INPUT...:
     single-linkage clusters of all INPUT sketches under the Mash distance D, computed on the GPU
     (each pair once, the clusters formed in device memory); one row per sketch on stdout in input
     order (member, representative, cluster index, cluster size) and a summary line on stderr.
@@ -610,6 +621,7 @@ def cmd_derep(argv: Sequence[str]) -> int:
       -r  a cluster's representative: its longest genome (longest) or its first member (first)
       -o  write PREFIX.msh holding the representatives only (the suffix is not doubled)
       -i  one sketch per sequence of a FASTA INPUT      -l  INPUTs list paths
+      --sparse  visit only the pairs that share a hash (the same clusters)
       -k -s -S  k-mer size, sketch size and seed for FASTA INPUTs when no INPUT is a .msh
                 (21, 1000, 42); otherwise the first .msh INPUT's parameters are used
     An INPUT ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU."""
@@ -633,7 +645,7 @@ def cmd_derep(argv: Sequence[str]) -> int:
     if db.n_refs == 0:
         print("ERROR: no sequences to sketch.", file=sys.stderr)
         return 1
-    res = dr.cluster(gpu, db, a.max_dist)
+    res = dr.cluster(gpu, db, a.max_dist, sparse=a.sparse)
     reps = dr.representatives(res.labels, db.lengths, a.rule)
     sys.stdout.write("".join(l + "\n" for l in dr.format_rows(db, res.labels, reps)))
     print(f"derep: {db.n_refs} sketches, {res.n_links} links, {len(reps)} clusters", file=sys.stderr)

@@ -34,7 +34,12 @@
 //   link       : the same filter over the r < q entries of a dense block, each passing pair united
 //                in a union-find over the sketches (hymet_mash_link; the rules stand at uf_find);
 //                labels: every sketch's root, the smallest index of its component.
+//   sp_*       : the same CSR as select over the dense block, for a threshold below 1, from the
+//                pairs that share a hash only (hymet_mash_dist_sparse): postings sorted by hash,
+//                one key per shared hash of a pair, keys sorted, runs of cmin or more keys go to
+//                the pair routine.  link_edges: the union-find over that CSR.
 #include "mm_common.hpp"
+#include "sort.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -362,6 +367,233 @@ __global__ __launch_bounds__(kThreads) void labels_kernel(int32_t *__restrict__ 
     if (i < n) label[i] = uf_find(parent, (int32_t)i, err);
 }
 
+// one workgroup per row block of the CSR: row `row` is sketch q_begin + row, its entries the
+// sketches it is united with (hymet_mash_link_edges)
+__global__ __launch_bounds__(kThreads) void link_edges_kernel(const int64_t *__restrict__ row_off, int64_t n_rows,
+                                                              int64_t q_begin, const int32_t *__restrict__ ref_idx,
+                                                              int32_t *__restrict__ parent,
+                                                              unsigned long long *__restrict__ n_links,
+                                                              int32_t *__restrict__ err) {
+    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        const int32_t q = (int32_t)(q_begin + row);
+        const int64_t e1 = row_off[row + 1];
+        for (int64_t e = row_off[row] + threadIdx.x; e < e1; e += kThreads) {
+            const int32_t r = ref_idx[e];
+            if (r < 0)
+                __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                uf_unite(parent, q, r, err);
+        }
+    }
+    // the entry count is the CSR's span: one integer atomic per call
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t t = row_off[n_rows] - row_off[0];
+        if (t > 0) atomicAdd(n_links, (unsigned long long)t);
+    }
+}
+
+// ---- sparse dist (hymet_mash_dist_sparse; DESIGN.md §3 "Sparse dist")
+// A posting is (hash, id): ids are the references first, then the queries of the row range
+// (SpSide::first_q = n_ref); in tri mode the sketches [0, q_end) once each, a sketch being a
+// query when its id lies in the row range (first_q = q_begin).  After the stable sort by hash a
+// run of equal hashes holds ascending ids, so the partners of a query-side posting at i --
+// the reference postings of its run, or every earlier posting in tri mode -- are the cnt[i]
+// postings from the run's start on.
+
+// one workgroup per id writes the first min(len, s) hashes of its sketch
+__global__ __launch_bounds__(kThreads) void sp_postings_kernel(const uint64_t *__restrict__ rh,
+                                                               const int64_t *__restrict__ roff, int64_t n_side_ref,
+                                                               const uint64_t *__restrict__ qh,
+                                                               const int64_t *__restrict__ qoff, int64_t q_begin,
+                                                               const int64_t *__restrict__ poff, int s,
+                                                               uint64_t *__restrict__ key, uint32_t *__restrict__ id) {
+    const int64_t i = blockIdx.x;
+    const bool is_ref = i < n_side_ref;  // workgroup-uniform
+    const uint64_t *h = is_ref ? rh : qh;
+    const int64_t *off = is_ref ? roff : qoff;
+    const int64_t k = is_ref ? i : q_begin + (i - n_side_ref);
+    const int64_t b = off[k], p = poff[i];
+    const int len = (int)min((int64_t)s, off[k + 1] - b);
+    for (int e = threadIdx.x; e < len; e += kThreads) {
+        key[p + e] = h[b + e];
+        id[p + e] = (uint32_t)i;
+    }
+}
+
+// mark[i] = i at the start of a run of equal hashes, else 0: its running maximum is the run start
+__global__ __launch_bounds__(kThreads) void sp_mark_kernel(const uint64_t *__restrict__ key, int64_t n,
+                                                           int32_t *__restrict__ mark) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) mark[i] = i > 0 && key[i] == key[i - 1] ? 0 : (int32_t)i;
+}
+
+// keys owed by every posting (cnt has n + 1 entries, the last 0 for the scan's total)
+template <bool TRI>
+__global__ __launch_bounds__(kThreads) void sp_count_kernel(const uint32_t *__restrict__ id,
+                                                            const int32_t *__restrict__ run_start, int64_t n,
+                                                            uint32_t first_q, uint32_t *__restrict__ cnt) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i > n) return;
+    uint32_t c = 0;
+    if (i < n && id[i] >= first_q) {
+        const int32_t r0 = run_start[i];
+        if (TRI) {
+            c = (uint32_t)((int32_t)i - r0);
+        } else {  // the run's reference postings come first: the first query-side one in [r0, i)
+            int32_t lo = r0, hi = (int32_t)i;
+            while (lo < hi) {
+                const int32_t mid = lo + ((hi - lo) >> 1);
+                if (id[mid] < first_q)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            c = (uint32_t)(lo - r0);
+        }
+    }
+    cnt[i] = c;
+}
+
+// One workgroup per 256 consecutive postings: their key offsets, run starts and rows are staged
+// in LDS, then the 256 lanes sweep the workgroup's keys (contiguous in the output, and in the id
+// array inside one posting's share), finding each key's posting by binary search in LDS -- as
+// write_anchor_keys_kernel does, since one run can hold thousands of postings.
+__global__ __launch_bounds__(kThreads) void sp_emit_kernel(const uint32_t *__restrict__ id,
+                                                           const int32_t *__restrict__ run_start,
+                                                           const int64_t *__restrict__ eoff, int64_t n, uint32_t first_q,
+                                                           int rb, uint64_t *__restrict__ key) {
+    __shared__ int64_t s_a[kThreads + 1];
+    __shared__ int32_t s_r[kThreads];
+    __shared__ uint32_t s_q[kThreads];
+    const int tid = threadIdx.x;
+    const int64_t m0 = (int64_t)blockIdx.x * kThreads;
+    const int cnt = (int)min((int64_t)kThreads, n - m0);
+    if (tid < cnt) {
+        s_a[tid] = eoff[m0 + tid];
+        s_r[tid] = run_start[m0 + tid];
+        s_q[tid] = id[m0 + tid] - first_q;  // only read for a query-side posting
+    }
+    if (tid == 0) s_a[cnt] = eoff[m0 + cnt];
+    __syncthreads();
+    const int64_t a0 = s_a[0], a1 = s_a[cnt];
+    for (int64_t a = a0 + tid; a < a1; a += kThreads) {
+        int lo = 0, hi = cnt - 1;  // last posting with s_a <= a (its share is non-empty)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_a[mid] <= a)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        const uint32_t r = id[(int64_t)s_r[lo] + (a - s_a[lo])];
+        key[a] = (uint64_t)s_q[lo] << rb | r;
+    }
+}
+
+// The pairs of two empty sketches, which no posting finds: empty query j (row eq_row[j]) pairs
+// with the first epre[j + 1] - epre[j] empty references er[]; key e belongs to the last j with
+// epre[j] <= e.
+__global__ __launch_bounds__(kThreads) void sp_empty_keys_kernel(const uint32_t *__restrict__ eq_row,
+                                                                 const int64_t *__restrict__ epre, int64_t n_eq,
+                                                                 const uint32_t *__restrict__ er, int64_t n_keys, int rb,
+                                                                 uint64_t *__restrict__ key) {
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= n_keys) return;
+    int64_t lo = 0, hi = n_eq - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (epre[mid] <= e)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    key[e] = (uint64_t)eq_row[lo] << rb | er[e - epre[lo]];
+}
+
+// keep[i] = 1 at the first key of a run that is a candidate: cmin or more equal keys (sorted, so
+// the key cmin - 1 places on decides), or a pair of two empty sketches (a run of one; looked up
+// only when the call added such keys).  keep has n + 1 entries, the last 0.
+__global__ __launch_bounds__(kThreads) void sp_runs_kernel(const uint64_t *__restrict__ key, int64_t n, int cmin, int rb,
+                                                           const int64_t *__restrict__ roff,
+                                                           const int64_t *__restrict__ qoff, int64_t q_begin,
+                                                           int has_empty, uint32_t *__restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i > n) return;
+    bool kp = false;
+    if (i < n) {
+        const uint64_t k = key[i];
+        if (i == 0 || key[i - 1] != k) {
+            kp = i + cmin - 1 < n && key[i + cmin - 1] == k;
+            if (!kp && has_empty) {
+                const int64_t r = (int64_t)(k & ((1ull << rb) - 1)), q = q_begin + (int64_t)(k >> rb);
+                kp = roff[r + 1] == roff[r] && qoff[q + 1] == qoff[q];
+            }
+        }
+    }
+    keep[i] = kp ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kThreads) void sp_compact_kernel(const uint64_t *__restrict__ key,
+                                                              const uint32_t *__restrict__ keep,
+                                                              const int64_t *__restrict__ pos, int64_t n,
+                                                              uint64_t *__restrict__ cand) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n && keep[i]) cand[pos[i]] = key[i];
+}
+
+// one wave per candidate: the pair routine on the two lists in global memory, and the filter
+// (pass has n_cand + 1 entries, the last zeroed by the host)
+__global__ __launch_bounds__(kThreads) void sp_exact_kernel(const uint64_t *__restrict__ rh,
+                                                            const int64_t *__restrict__ roff,
+                                                            const uint64_t *__restrict__ qh,
+                                                            const int64_t *__restrict__ qoff, int64_t q_begin,
+                                                            const uint64_t *__restrict__ cand, int64_t n_cand, int rb,
+                                                            int s, const uint16_t *__restrict__ minc,
+                                                            uint32_t *__restrict__ val, uint32_t *__restrict__ pass) {
+    const int64_t c = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (c >= n_cand) return;  // wave-uniform
+    const uint64_t k = cand[c];
+    const int64_t r = (int64_t)(k & ((1ull << rb) - 1)), q = q_begin + (int64_t)(k >> rb);
+    const int64_t b0 = roff[r], b1 = qoff[q];
+    const int la = (int)min((int64_t)s, roff[r + 1] - b0), lb = (int)min((int64_t)s, qoff[q + 1] - b1);
+    const uint32_t v = wave_pair(rh + b0, la, qh + b1, lb, s);
+    if ((threadIdx.x & 63) == 0) {
+        val[c] = v;
+        pass[c] = select_pass(v, minc, s) ? 1u : 0u;
+    }
+}
+
+// row_off[row], row in [0, rows]: the passing entries before the row's first candidate (the
+// candidates are in (row, reference) order; ppos has n_cand + 1 entries)
+__global__ __launch_bounds__(kThreads) void sp_row_off_kernel(const uint64_t *__restrict__ cand, int64_t n_cand, int rb,
+                                                              const int64_t *__restrict__ ppos, int64_t rows,
+                                                              int64_t *__restrict__ row_off) {
+    const int64_t row = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (row > rows) return;
+    const uint64_t first = (uint64_t)row << rb;
+    int64_t lo = 0, hi = n_cand;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (cand[mid] < first)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    row_off[row] = ppos[lo];
+}
+
+__global__ __launch_bounds__(kThreads) void sp_write_kernel(const uint64_t *__restrict__ cand,
+                                                            const uint32_t *__restrict__ val,
+                                                            const uint32_t *__restrict__ pass,
+                                                            const int64_t *__restrict__ ppos, int64_t n_cand, int rb,
+                                                            int32_t *__restrict__ out_ref, uint32_t *__restrict__ out_val) {
+    const int64_t c = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (c >= n_cand || !pass[c]) return;
+    const int64_t p = ppos[c];  // below the total, which the host checked against the capacity
+    out_ref[p] = (int32_t)(cand[c] & ((1ull << rb) - 1));
+    out_val[p] = val[c];
+}
+
 // path 0: tiled where the tile fits, 1: always the plain kernel; tq 0: the default tile
 struct DistCfg {
     int path = 0, tq = 0;
@@ -563,6 +795,247 @@ int hymet_mash_labels(hymet_ctx *ctx, int32_t *d_parent, int64_t n, int32_t *d_l
         HY_HIP(hipMemsetAsync(err, 0, 4, st));  // left zeroed for the next clustering
         return hymet::fail(HYMET_E_ARG, "hymet_mash_labels: a parent outside [0, x] was met");
     }
+    return HYMET_OK;
+}
+
+int hymet_mash_link_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_rows, int64_t q_begin,
+                          const int32_t *d_ref_idx, int32_t *d_parent, uint64_t *d_n_links) {
+    HY_ARG(ctx, "hymet_mash_link_edges: null context");
+    HY_ARG(n_rows >= 0 && q_begin >= 0 && q_begin < (1ll << 31) && n_rows < (1ll << 31) - q_begin,
+           "hymet_mash_link_edges: rows outside [0, 2^31)");
+    HY_ARG(d_n_links, "hymet_mash_link_edges: null argument");
+    HY_HIP(hipSetDevice(ctx->device));
+    if (n_rows == 0) return HYMET_OK;
+    HY_ARG(d_row_off && d_ref_idx && d_parent, "hymet_mash_link_edges: null argument");
+    const int64_t nb = std::min<int64_t>(n_rows, (int64_t)ctx->n_cu * 8);
+    hymet::ProfScope _ps(ctx, "mash_link_edges", 8.0 * (double)n_rows);
+    hipLaunchKernelGGL(link_edges_kernel, dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, d_row_off, n_rows, q_begin,
+                       d_ref_idx, d_parent, reinterpret_cast<unsigned long long *>(d_n_links),
+                       ctx->dctr + hymet::mm::kCtrUfErr);
+    HY_CHECK_LAUNCH("link_edges_kernel");
+    return HYMET_OK;
+}
+
+int hymet_mash_dist_sparse(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t n_ref_hashes, const int64_t *d_ref_off,
+                           int64_t n_ref, const uint64_t *d_qry_hashes, int64_t n_qry_hashes, const int64_t *d_qry_off,
+                           int64_t n_qry, int64_t q_begin, int64_t q_end, int32_t s, int tri,
+                           const uint16_t *d_min_common, int32_t cmin, int64_t max_pairs, int64_t *d_row_off,
+                           int32_t *d_ref_idx, uint32_t *d_val, int64_t cap, int64_t *total,
+                           hymet_sparse_counters *counters) {
+    using hymet::cdiv;
+    using hymet::mm::DevBuf;
+    HY_ARG(ctx && total && counters, "hymet_mash_dist_sparse: null argument");
+    *total = 0;
+    counters->postings = counters->emitted = counters->candidates = 0;
+    HY_ARG(s >= 1 && s <= kMaxS, "hymet_mash_dist_sparse: sketch size must be in 1.." + std::to_string(kMaxS));
+    HY_ARG(n_ref >= 0 && n_ref < (1ll << 31) && n_qry >= 0 && n_ref_hashes >= 0 && n_qry_hashes >= 0,
+           "hymet_mash_dist_sparse: count out of range");
+    HY_ARG(q_begin >= 0 && q_begin <= q_end && q_end <= n_qry, "hymet_mash_dist_sparse: row range outside [0, n_qry]");
+    HY_ARG(q_end - q_begin < (1ll << 31) - 1, "hymet_mash_dist_sparse: more than 2^31 rows in one call");
+    HY_ARG(d_ref_off && d_qry_off, "hymet_mash_dist_sparse: null offsets");
+    HY_ARG((n_ref_hashes == 0 || d_ref_hashes) && (n_qry_hashes == 0 || d_qry_hashes),
+           "hymet_mash_dist_sparse: null hashes");
+    HY_ARG(!tri || (d_qry_hashes == d_ref_hashes && d_qry_off == d_ref_off && n_qry == n_ref && n_qry_hashes == n_ref_hashes),
+           "hymet_mash_dist_sparse: tri mode takes one DB as both arguments");
+    HY_ARG(d_row_off && d_min_common, "hymet_mash_dist_sparse: null argument");
+    HY_ARG(cmin >= 1 && max_pairs >= 0 && cap >= 0, "hymet_mash_dist_sparse: cmin below 1 or a negative bound");
+    HY_HIP(hipSetDevice(ctx->device));
+    std::vector<int64_t> roff, qoff_own;
+    int rc = check_offsets(ctx, d_ref_off, n_ref, n_ref_hashes, tri ? "sketch" : "reference", &roff);
+    if (rc) return rc;
+    if (!tri) {
+        rc = check_offsets(ctx, d_qry_off, n_qry, n_qry_hashes, "query", &qoff_own);
+        if (rc) return rc;
+    }
+    const std::vector<int64_t> &qoff = tri ? roff : qoff_own;
+    hipStream_t st = ctx->stream;
+    const int64_t rows = q_end - q_begin;
+    auto no_entries = [&]() -> int {
+        HY_HIP(hipMemsetAsync(d_row_off, 0, 8 * (size_t)(rows + 1), st));
+        HY_HIP(hipStreamSynchronize(st));
+        return HYMET_OK;
+    };
+    if (rows == 0 || n_ref == 0) return no_entries();
+    const int rb = hymet::mm::bits_for(n_ref), kb = rb + hymet::mm::bits_for(rows - 1);  // at most 31 + 31
+
+    // ids and the posting offset of each, from the offsets the check copied
+    const int64_t n_side_ref = tri ? q_end : n_ref, n_ids = tri ? q_end : n_ref + rows;
+    const uint32_t first_q = (uint32_t)(tri ? q_begin : n_ref);
+    HY_ARG(n_ids < (1ll << 31), "hymet_mash_dist_sparse: more than 2^31 sketches in one call");
+    std::vector<int64_t> poff((size_t)n_ids + 1, 0);
+    for (int64_t i = 0; i < n_ids; i++) {
+        const int64_t len = i < n_side_ref ? roff[i + 1] - roff[i]
+                                           : qoff[q_begin + (i - n_side_ref) + 1] - qoff[q_begin + (i - n_side_ref)];
+        poff[i + 1] = poff[i] + std::min<int64_t>(s, len);
+    }
+    const int64_t P = poff[n_ids];
+    HY_ARG(P < (1ll << 31), "hymet_mash_dist_sparse: more than 2^31 postings in one call: split the row range");
+    counters->postings = P;
+    // the pairs of two empty sketches: empty query j with the empty references before epre's step
+    std::vector<uint32_t> er, eq_row;
+    std::vector<int64_t> epre(1, 0);
+    for (int64_t r = 0; r < n_side_ref; r++)
+        if (roff[r + 1] == roff[r]) er.push_back((uint32_t)r);
+    {
+        size_t below = 0;  // tri: the empty sketches before q
+        for (int64_t q = q_begin; q < q_end && !er.empty(); q++) {
+            if (qoff[q + 1] != qoff[q]) continue;
+            while (tri && below < er.size() && (int64_t)er[below] < q) below++;
+            const int64_t k = tri ? (int64_t)below : (int64_t)er.size();
+            if (k == 0) continue;
+            eq_row.push_back((uint32_t)(q - q_begin));
+            epre.push_back(epre.back() + k);
+        }
+    }
+    const int64_t n_empty = epre.back();
+
+    int64_t emitted = 0;
+    DevBuf key0, key1;  // the pair keys and the sort's second buffer
+    {
+        // what the emit reads of the postings; released before the keys are sorted
+        DevBuf d_poff, pk0, pk1, pv0, pv1, mark, run_start, eoff, mpart;
+        uint32_t *ids = nullptr;
+        if (P > 0) {
+            HY_HIP(d_poff.alloc(8 * (size_t)(n_ids + 1), st));
+            HY_HIP(pk0.alloc(8 * (size_t)P, st));
+            HY_HIP(pk1.alloc(8 * (size_t)P, st));
+            HY_HIP(pv0.alloc(4 * (size_t)P, st));
+            HY_HIP(pv1.alloc(4 * (size_t)P, st));
+            HY_HIP(mark.alloc(4 * (size_t)(P + 1), st));
+            HY_HIP(run_start.alloc(4 * (size_t)P, st));
+            HY_HIP(eoff.alloc(8 * (size_t)(P + 1), st));
+            uint64_t *kk = pk0.as<uint64_t>(), *kka = pk1.as<uint64_t>();
+            uint32_t *vv = pv0.as<uint32_t>(), *vva = pv1.as<uint32_t>();
+            {
+                hymet::ProfScope _ps(ctx, "sparse_postings", 20.0 * (double)P);
+                HY_HIP(hipMemcpyAsync(d_poff.p, poff.data(), 8 * (size_t)(n_ids + 1), hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(sp_postings_kernel, dim3((unsigned)n_ids), dim3(kThreads), 0, st, d_ref_hashes, d_ref_off,
+                                   n_side_ref, d_qry_hashes, d_qry_off, q_begin, d_poff.as<int64_t>(), (int)s, kk, vv);
+                HY_CHECK_LAUNCH("sp_postings_kernel");
+            }
+            {
+                hymet::ProfScope _ps(ctx, "sparse_sort_postings", 8.0 * 24.0 * (double)P);
+                rc = hymet::mm::radix_sort_pairs(ctx, kk, kka, vv, vva, P, 0, 64);
+                if (rc) return rc;
+            }
+            ids = vv;
+            {
+                hymet::ProfScope _ps(ctx, "sparse_count", 32.0 * (double)P);
+                hipLaunchKernelGGL(sp_mark_kernel, dim3((unsigned)cdiv(P, kThreads)), dim3(kThreads), 0, st, kk, P,
+                                   mark.as<int32_t>());
+                HY_CHECK_LAUNCH("sp_mark_kernel");
+                rc = hymet::mm::inclusive_max_scan_i32(ctx, mark.as<int32_t>(), run_start.as<int32_t>(), P, mpart);
+                if (rc) return rc;
+                // the marks are read; their buffer takes the counts
+                const dim3 g((unsigned)cdiv(P + 1, kThreads));
+                if (tri)
+                    hipLaunchKernelGGL(sp_count_kernel<true>, g, dim3(kThreads), 0, st, ids, run_start.as<int32_t>(), P,
+                                       first_q, mark.as<uint32_t>());
+                else
+                    hipLaunchKernelGGL(sp_count_kernel<false>, g, dim3(kThreads), 0, st, ids, run_start.as<int32_t>(), P,
+                                       first_q, mark.as<uint32_t>());
+                HY_CHECK_LAUNCH("sp_count_kernel");
+                rc = hymet::mm::exclusive_scan_u32_i64(ctx, mark.as<uint32_t>(), eoff.as<int64_t>(), P + 1, &emitted);
+                if (rc) return rc;
+            }
+        }
+        counters->emitted = emitted;
+        if (emitted > max_pairs || n_empty > max_pairs - emitted) {
+            *total = -1;
+            return hymet::fail(HYMET_E_CAPACITY, "hymet_mash_dist_sparse: " + std::to_string(emitted) + " pair keys and " +
+                                                     std::to_string(n_empty) + " empty pairs, budget " +
+                                                     std::to_string(max_pairs));
+        }
+        const int64_t N = emitted + n_empty;
+        if (N == 0) return no_entries();
+        HY_HIP(key0.alloc(8 * (size_t)N, st));
+        HY_HIP(key1.alloc(8 * (size_t)N, st));
+        hymet::ProfScope _ps(ctx, "sparse_emit", 12.0 * (double)N);
+        if (emitted > 0) {
+            hipLaunchKernelGGL(sp_emit_kernel, dim3((unsigned)cdiv(P, kThreads)), dim3(kThreads), 0, st, ids,
+                               run_start.as<int32_t>(), eoff.as<int64_t>(), P, first_q, rb, key0.as<uint64_t>());
+            HY_CHECK_LAUNCH("sp_emit_kernel");
+        }
+        if (n_empty > 0) {
+            DevBuf d_eq, d_epre, d_er;
+            HY_HIP(d_eq.alloc(4 * eq_row.size(), st));
+            HY_HIP(d_epre.alloc(8 * epre.size(), st));
+            HY_HIP(d_er.alloc(4 * er.size(), st));
+            HY_HIP(hipMemcpyAsync(d_eq.p, eq_row.data(), 4 * eq_row.size(), hipMemcpyHostToDevice, st));
+            HY_HIP(hipMemcpyAsync(d_epre.p, epre.data(), 8 * epre.size(), hipMemcpyHostToDevice, st));
+            HY_HIP(hipMemcpyAsync(d_er.p, er.data(), 4 * er.size(), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(sp_empty_keys_kernel, dim3((unsigned)cdiv(n_empty, kThreads)), dim3(kThreads), 0, st,
+                               d_eq.as<uint32_t>(), d_epre.as<int64_t>(), (int64_t)eq_row.size(), d_er.as<uint32_t>(), n_empty,
+                               rb, key0.as<uint64_t>() + emitted);
+            HY_CHECK_LAUNCH("sp_empty_keys_kernel");
+        }
+    }
+    const int64_t N = emitted + n_empty;
+    uint64_t *keys = key0.as<uint64_t>(), *keys_alt = key1.as<uint64_t>();
+    {
+        // the library's sort moves a value with every key: a byte nobody reads
+        DevBuf b0, b1;
+        HY_HIP(b0.alloc((size_t)N, st));
+        HY_HIP(b1.alloc((size_t)N, st));
+        uint8_t *bb = b0.as<uint8_t>(), *bba = b1.as<uint8_t>();
+        hymet::ProfScope _ps(ctx, "sparse_sort_keys", (double)((kb + 7) / 8) * 18.0 * (double)N);
+        rc = hymet::mm::radix_sort_pairs(ctx, keys, keys_alt, bb, bba, N, 0, kb);
+        if (rc) return rc;
+    }
+    int64_t n_cand = 0;
+    DevBuf cand;
+    {
+        DevBuf keep, kpos;
+        HY_HIP(keep.alloc(4 * (size_t)(N + 1), st));
+        HY_HIP(kpos.alloc(8 * (size_t)(N + 1), st));
+        hymet::ProfScope _ps(ctx, "sparse_runs", 28.0 * (double)N);
+        hipLaunchKernelGGL(sp_runs_kernel, dim3((unsigned)cdiv(N + 1, kThreads)), dim3(kThreads), 0, st, keys, N, (int)cmin, rb,
+                           d_ref_off, d_qry_off, q_begin, n_empty > 0 ? 1 : 0, keep.as<uint32_t>());
+        HY_CHECK_LAUNCH("sp_runs_kernel");
+        rc = hymet::mm::exclusive_scan_u32_i64(ctx, keep.as<uint32_t>(), kpos.as<int64_t>(), N + 1, &n_cand);
+        if (rc) return rc;
+        counters->candidates = n_cand;
+        if (n_cand == 0) return no_entries();
+        HY_HIP(cand.alloc(8 * (size_t)n_cand, st));
+        hipLaunchKernelGGL(sp_compact_kernel, dim3((unsigned)cdiv(N, kThreads)), dim3(kThreads), 0, st, keys,
+                           keep.as<uint32_t>(), kpos.as<int64_t>(), N, cand.as<uint64_t>());
+        HY_CHECK_LAUNCH("sp_compact_kernel");
+    }
+    key0.release();
+    key1.release();
+    HY_ARG(cdiv(n_cand, kWaves) < (1ll << 31), "hymet_mash_dist_sparse: more than 2^33 candidates in one call");
+    DevBuf val, pass, ppos;
+    HY_HIP(val.alloc(4 * (size_t)n_cand, st));
+    HY_HIP(pass.alloc(4 * (size_t)(n_cand + 1), st));
+    HY_HIP(ppos.alloc(8 * (size_t)(n_cand + 1), st));
+    {
+        hymet::ProfScope _ps(ctx, "sparse_exact", 16.0 * (double)s * (double)n_cand);
+        HY_HIP(hipMemsetAsync(pass.as<uint32_t>() + n_cand, 0, 4, st));
+        hipLaunchKernelGGL(sp_exact_kernel, dim3((unsigned)cdiv(n_cand, kWaves)), dim3(kThreads), 0, st, d_ref_hashes, d_ref_off,
+                           d_qry_hashes, d_qry_off, q_begin, cand.as<uint64_t>(), n_cand, rb, (int)s, d_min_common,
+                           val.as<uint32_t>(), pass.as<uint32_t>());
+        HY_CHECK_LAUNCH("sp_exact_kernel");
+    }
+    hymet::ProfScope _ps(ctx, "sparse_csr", 24.0 * (double)n_cand + 8.0 * (double)rows);
+    int64_t t = 0;
+    rc = hymet::mm::exclusive_scan_u32_i64(ctx, pass.as<uint32_t>(), ppos.as<int64_t>(), n_cand + 1, &t);
+    if (rc) return rc;
+    *total = t;
+    hipLaunchKernelGGL(sp_row_off_kernel, dim3((unsigned)cdiv(rows + 1, kThreads)), dim3(kThreads), 0, st, cand.as<uint64_t>(),
+                       n_cand, rb, ppos.as<int64_t>(), rows, d_row_off);
+    HY_CHECK_LAUNCH("sp_row_off_kernel");
+    if (t > cap) {
+        HY_HIP(hipStreamSynchronize(st));
+        return hymet::fail(HYMET_E_CAPACITY, "hymet_mash_dist_sparse: " + std::to_string(t) + " entries, capacity " +
+                                                 std::to_string(cap));
+    }
+    if (t > 0) {
+        HY_ARG(d_ref_idx && d_val, "hymet_mash_dist_sparse: null output");
+        hipLaunchKernelGGL(sp_write_kernel, dim3((unsigned)cdiv(n_cand, kThreads)), dim3(kThreads), 0, st, cand.as<uint64_t>(),
+                           val.as<uint32_t>(), pass.as<uint32_t>(), ppos.as<int64_t>(), n_cand, rb, d_ref_idx, d_val);
+        HY_CHECK_LAUNCH("sp_write_kernel");
+    }
+    HY_HIP(hipStreamSynchronize(st));
     return HYMET_OK;
 }
 

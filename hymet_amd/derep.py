@@ -6,7 +6,9 @@ Device work (libhymet_gpu.so, csrc/mash_dist.hip): `hymet_mash_dist_tri` compute
 triangle of the DB against itself (every pair once), `hymet_mash_link` applies `dist -d`'s filter
 to it and unites each passing pair in a union-find that stays in HBM -- no edge list is built --
 and `hymet_mash_labels` names every sketch's cluster by its smallest member.  Host work here:
-blocking, the choice of representatives, the reduced DB and the text.
+blocking, the choice of representatives, the reduced DB and the text.  With sparse=True the
+links come from `hymet_mash_dist_sparse` (the pairs that share a hash only) and are united by
+`hymet_mash_link_edges`; the clusters are the same.
 
 `triangle_lines` prints the triangle itself in the format of Mash's `triangle` command as
 remembered; like the rest of dist it is PARITY-UNPINNED (mashdist.py): no Mash binary is
@@ -32,12 +34,18 @@ def _block_rows(n: int, block_bytes: int) -> int:
     return max(1, int(block_bytes) // (4 * max(n, 1)))
 
 
-def cluster(gpu, db: SketchDB, max_dist: float, block_bytes: int = 1 << 30) -> ClusterResult:
+def cluster(gpu, db: SketchDB, max_dist: float, block_bytes: int = 1 << 30, sparse: bool = False,
+            plan: list = None) -> ClusterResult:
     """Single-linkage clusters of db's sketches: two sketches share a cluster when a chain of
     pairs with distance() <= max_dist joins them.  0 <= max_dist < 1.  The DB is uploaded once;
     per block of rows the triangle kernel and the link kernel are queued on one stream with
     nothing copied back in between; the labels and the link count come back once, at the end.
-    The result does not depend on block_bytes."""
+    The result does not depend on block_bytes.
+    sparse: the same result from the pairs that share a hash only -- hymet_mash_dist_sparse in
+    tri mode per row range (mashdist.sparse_ranges: halved on an emission overflow, the dense
+    kernels for a range no larger than a dense block that still overflows), its CSR united on the
+    device by hymet_mash_link_edges.  plan, when given, receives (path, q0, q1, counters) per
+    range."""
     if not 0.0 <= max_dist < 1.0:          # also refuses NaN
         raise ValueError(f"cluster: max_dist {max_dist} outside [0, 1)")
     s = md.check_compatible(db, db, warn=False)
@@ -50,6 +58,21 @@ def cluster(gpu, db: SketchDB, max_dist: float, block_bytes: int = 1 << 30) -> C
     label = gpu.empty(max(n, 1), torch.int32)
     n_links = gpu.zeros(1, torch.int64)
     rows = _block_rows(n, block_bytes)
+    if sparse:
+        cmin = md.candidate_min_common(md.min_common_table(s, db.k, max_dist))
+        max_pairs = max(0, int(block_bytes) // 16)
+        for path, q0, q1, got in md.sparse_ranges(n, rows, lambda a, b: md.sparse_block(gpu, dev, dev, a, b, s, table, cmin,
+                                                                                        max_pairs, tri=True)):
+            if plan is not None:
+                plan.append((path, q0, q1, got[4] if got else None))
+            if path == "dense":
+                block = gpu.empty(max(1, (q1 - q0) * n), torch.int32)
+                gpu.call("hymet_mash_dist_tri", ptr(dev.hashes), dev.n_hashes, ptr(dev.offsets), n, q0, q1, s, ptr(block))
+                gpu.call("hymet_mash_link", ptr(block), q1 - q0, n, q0, ptr(table), s, ptr(parent), ptr(n_links))
+            else:
+                gpu.call("hymet_mash_link_edges", ptr(got[0]), q1 - q0, q0, ptr(got[1]), ptr(parent), ptr(n_links))
+        gpu.call("hymet_mash_labels", ptr(parent), n, ptr(label))
+        return ClusterResult(label[:n].cpu().numpy().astype(np.int32), int(n_links.cpu().item()))
     block = gpu.empty(max(1, min(rows, n) * n), torch.int32)
     for q0 in range(0, n, rows):
         q1 = min(n, q0 + rows)

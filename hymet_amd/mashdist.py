@@ -8,6 +8,8 @@ s smallest values of the two lists' union -- and `hymet_mash_dist_select` keeps 
 pass a distance threshold.  Host work here: the distance and p-value arithmetic in double
 (the one `distance()` below both formats the output and builds the device filter's table, so
 the filter agrees exactly with the printed numbers), blocking, and the text.
+`hymet_mash_dist_sparse` gives the filtered result of a threshold below 1 from the pairs that
+share a hash only (opt-in: sparse_blocks; DESIGN.md §3 Sparse dist).
 
 The semantics restate Mash's `dist` command from memory of its behaviour.  No Mash binary is
 available to check them against: they are PARITY-UNPINNED, like the .msh schema (msh.py) and
@@ -184,14 +186,115 @@ def select_block(gpu, block, n_rows: int, n_ref: int, table, s: int, cap: int = 
     return row_off.cpu().numpy(), idx[:n].cpu().numpy(), val[:n].cpu().numpy().view(np.uint32)
 
 
-def dist_blocks(gpu, ref_db: SketchDB, qry_db: SketchDB, max_dist: float = 1.0,
-                block_bytes: int = 1 << 30) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+def candidate_min_common(table) -> int:
+    """cmin of the sparse path: the fewest shared hashes a pair that passes `table`
+    (min_common_table) can have, the smallest t[denom] over denom >= 1.  At least 1 for
+    max_dist < 1, where common = 0 never passes; a pair of two empty sketches (denom 0) shares
+    nothing and is handled on its own (hymet_mash_dist_sparse)."""
+    t = np.asarray(table).astype(np.int64)
+    if len(t) < 2:
+        raise ValueError("candidate_min_common: the table has no denom >= 1")
+    return int(t[1:].min())
+
+
+def sparse_ranges(q_end: int, rows: int, attempt, q_begin: int = 0):
+    """The blocking policy of the sparse path, shared by sparse_blocks and derep.cluster: the row
+    ranges in ascending order, starting with the whole of [q_begin, q_end).  attempt(q0, q1)
+    returns None on an emission overflow; the range is then halved, and a range of at most
+    `rows` rows (the dense path's block) is handed out as ("dense", q0, q1, None) instead.
+    Yields ("sparse", q0, q1, what attempt returned) otherwise."""
+    todo = [(q_begin, q_end)]
+    while todo:
+        q0, q1 = todo.pop()
+        if q1 <= q0:
+            continue
+        got = attempt(q0, q1)
+        if got is not None:
+            yield "sparse", q0, q1, got
+        elif q1 - q0 <= rows:
+            yield "dense", q0, q1, None
+        else:
+            mid = (q0 + q1) // 2
+            todo += [(mid, q1), (q0, mid)]
+
+
+def sparse_block(gpu, ref: DeviceSketches, qry: DeviceSketches, q_begin: int, q_end: int, s: int, table, cmin: int,
+                 max_pairs: int, tri: bool = False, cap: int = 0):
+    """One hymet_mash_dist_sparse call over the rows [q_begin, q_end): (row_off int64
+    [rows + 1], ref index int32, packed value int32, total, counters) with the arrays on the
+    device, or None when the range emits more than max_pairs pair keys.  Retries once with the
+    reported total when the first capacity was too small."""
+    from ._lib import SparseCounters, check, ptr
+    torch = gpu.torch
+    rows = q_end - q_begin
+    row_off = gpu.empty(rows + 1, torch.int64)
+    cap = int(cap) if cap > 0 else max(1024, min(int(max_pairs), rows * max(ref.n, 1)) // 16)
+    total, ctr = ctypes.c_int64(), SparseCounters()
+    while True:
+        idx = gpu.empty(cap, torch.int32)
+        val = gpu.empty(cap, torch.int32)
+        rc = gpu.lib.hymet_mash_dist_sparse(gpu.ctx, ptr(ref.hashes), ref.n_hashes, ptr(ref.offsets), ref.n, ptr(qry.hashes),
+                                            qry.n_hashes, ptr(qry.offsets), qry.n, int(q_begin), int(q_end), int(s),
+                                            int(bool(tri)), ptr(table), int(cmin), int(max_pairs), ptr(row_off), ptr(idx),
+                                            ptr(val), cap, ctypes.byref(total), ctypes.byref(ctr))
+        if rc == E_CAPACITY and total.value == -1:
+            return None
+        if rc == E_CAPACITY and total.value > cap:
+            cap = total.value
+            continue
+        check(rc, "hymet_mash_dist_sparse")
+        break
+    return row_off, idx, val, total.value, (ctr.postings, ctr.emitted, ctr.candidates)
+
+
+def sparse_blocks(gpu, ref_db: SketchDB, qry_db: SketchDB, max_dist: float, block_bytes: int = 1 << 30,
+                  plan: list = None) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+    """What dist_blocks yields for max_dist < 1 (ValueError otherwise), from the pairs that share
+    a hash only (hymet_mash_dist_sparse): exact, since a pair that shares none has distance 1.
+    A call may emit block_bytes // 16 pair keys; the whole query range is tried first, a range
+    that emits more is halved, and one no larger than dist_blocks' block that still does takes
+    the dense kernels.  The concatenated result depends neither on block_bytes nor on which
+    ranges fell back.  plan, when given, receives (path, q0, q1, counters) per range, path
+    "sparse" or "dense", counters (postings, emitted, candidates) or None."""
+    if not max_dist < 1.0:
+        raise ValueError(f"sparse_blocks: max_dist {max_dist} is not below 1")
+    s = check_compatible(ref_db, qry_db, warn=False)
+    torch = gpu.torch
+    ref, qry = DeviceSketches(gpu, ref_db), DeviceSketches(gpu, qry_db)
+    n_ref = ref.n
+    rows = max(1, int(block_bytes) // (4 * max(n_ref, 1)))
+    max_pairs = max(0, int(block_bytes) // 16)
+    host_table = min_common_table(s, ref_db.k, max_dist)
+    cmin = candidate_min_common(host_table)
+    table = torch.from_numpy(host_table.view(np.int16).copy()).to(gpu.dev)
+    for path, q0, q1, got in sparse_ranges(qry.n, rows, lambda a, b: sparse_block(gpu, ref, qry, a, b, s, table, cmin,
+                                                                                  max_pairs)):
+        if plan is not None:
+            plan.append((path, q0, q1, got[4] if got else None))
+        if n_ref == 0:
+            z = np.zeros(0, np.int32)
+            yield z, z, z, z
+            continue
+        if path == "dense":
+            row_off, ri, v = select_block(gpu, dist_block(gpu, ref, qry, q0, q1, s), q1 - q0, n_ref, table, s)
+        else:
+            d_off, d_idx, d_val, n, _ = got
+            row_off, ri, v = d_off.cpu().numpy(), d_idx[:n].cpu().numpy(), d_val[:n].cpu().numpy().view(np.uint32)
+        qi = np.repeat(np.arange(q0, q1, dtype=np.int32), np.diff(row_off))
+        yield qi, ri, (v >> 16).astype(np.int32), (v & 0xFFFF).astype(np.int32)
+
+
+def dist_blocks(gpu, ref_db: SketchDB, qry_db: SketchDB, max_dist: float = 1.0, block_bytes: int = 1 << 30,
+                sparse: bool = False) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
     """`mash dist` of two DBs on the device: yields (q_index, r_index, common, denom) int32
     arrays, query-major (for each query in DB order, the references in DB order), one tuple per
     block of queries.  Both DBs are uploaded once; a block holds as many queries as keep the
     dense result within block_bytes, and the concatenated result does not depend on it.
     max_dist >= 1: every pair; below, the pairs with distance() <= max_dist, filtered on the
-    device (min_common_table)."""
+    device (min_common_table).  sparse: the same result through sparse_blocks (max_dist < 1)."""
+    if sparse:
+        yield from sparse_blocks(gpu, ref_db, qry_db, max_dist, block_bytes)
+        return
     s = check_compatible(ref_db, qry_db, warn=False)
     torch = gpu.torch
     ref, qry = DeviceSketches(gpu, ref_db), DeviceSketches(gpu, qry_db)

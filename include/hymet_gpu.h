@@ -296,6 +296,41 @@ int hymet_mash_link(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int
  * when a link kernel since the last call, or this call's kernel, met a parent outside [0, x]
  * (the labels are then not to be used); the error word is cleared. */
 int hymet_mash_labels(hymet_ctx *ctx, int32_t *d_parent, int64_t n, int32_t *d_label);
+/* What one hymet_mash_dist_sparse call did: postings = (hash, sketch) entries sorted, emitted =
+ * pair keys the shared hashes produced (one per shared hash of a pair), candidates = distinct
+ * pairs that went to the exact pair routine. */
+typedef struct hymet_sparse_counters {
+    int64_t postings, emitted, candidates;
+} hymet_sparse_counters;
+/* `mash dist -d` for a threshold below 1 without the dense block: only the pairs that share a
+ * hash are visited (an inverted index over the hashes of both DBs), which is exact because a
+ * pair with common = 0 has distance 1.  Inputs and checks as hymet_mash_dist; output as
+ * hymet_mash_dist_select on hymet_mash_dist's block, byte for byte: d_row_off (rows + 1), then
+ * reference index and packed value per entry, rows in order, references in order inside a row.
+ * tri != 0: one DB against itself, the pairs r < q only; the query arguments must then repeat
+ * the reference arguments.  d_min_common: the s + 1 uint16 entries of the filter; cmin: the
+ * smallest d_min_common[denom] over denom >= 1 (>= 1), the fewest shared hashes a pair needs to
+ * be looked at.  Pairs of two empty sketches (denom 0) share nothing and are added on their own.
+ * max_pairs bounds the pair keys of one call (16 bytes of scratch each, and 2 for the sort);
+ * when the shared hashes produce more (counters->emitted, exact; the empty pairs count towards
+ * the bound too) the call returns HYMET_E_CAPACITY with *total = -1 and no output written: split
+ * the row range, or take the dense path.  *total = the number of entries otherwise (always
+ * set); when it exceeds cap the call returns HYMET_E_CAPACITY with d_row_off written and no
+ * entry written.  Count, the library's scan, write at every stage: the output is deterministic.
+ * n_ref and the row count below 2^31, fewer than 2^31 postings.  Synchronises. */
+int hymet_mash_dist_sparse(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t n_ref_hashes, const int64_t *d_ref_off,
+                           int64_t n_ref, const uint64_t *d_qry_hashes, int64_t n_qry_hashes, const int64_t *d_qry_off,
+                           int64_t n_qry, int64_t q_begin, int64_t q_end, int32_t s, int tri,
+                           const uint16_t *d_min_common, int32_t cmin, int64_t max_pairs, int64_t *d_row_off,
+                           int32_t *d_ref_idx, uint32_t *d_val, int64_t cap, int64_t *total,
+                           hymet_sparse_counters *counters);
+/* hymet_mash_link over an edge list instead of a dense block: unites q_begin + row with
+ * d_ref_idx[e] for every entry e of row `row` of the CSR (d_row_off: n_rows + 1 int64, as
+ * hymet_mash_dist_sparse with tri != 0 writes it) and adds the entry count to *d_n_links.
+ * d_parent, its invariants, the error word and hymet_mash_labels are those of hymet_mash_link;
+ * every index must lie inside d_parent.  Queued on the context's stream. */
+int hymet_mash_link_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_rows, int64_t q_begin,
+                          const int32_t *d_ref_idx, int32_t *d_parent, uint64_t *d_n_links);
 
 /* --------------------------------------------------- minimizer index (minimap2 -d)
  * Replaces `minimap2 -I2g -d reference.mmi combined_genomes.fasta` (scripts/minimap2.sh:12):
