@@ -1,5 +1,5 @@
 // Grouped anchor sort: the anchor words of a mapping batch (W = (rev | rid | rpos) << ybits | y,
-// one 64-bit word per anchor; write_anchor_keys_kernel / rechain_keys_kernel) into word order
+// one 64-bit word per anchor; write_anchor_keys_kernel) into word order
 // inside every query -- minimap2's radix sort of a query's anchors by x (map.c
 // collect_seed_hits -> radix_sort_128x), with the canonical full (x, y) tie order T1
 //  -- written out directly as the anchor set (x, y), so no unpack pass follows.
@@ -36,9 +36,9 @@
 // Equal keys after the device radix sort (one target position hit by several query
 // minimizers) are put in y order on write.
 // Index parts of more than 2047 targets use coarse bins of 2^cs consecutive targets (the
-// bin histogram always fits LDS), sorted inside by (low target bits, rpos, y).  The emitter
-// writes key / value pairs for the device sort of the whole batch instead where the word would
-// not fit 63 bits (anchor_word_ybits; the stage then returns 1).
+// bin histogram always fits LDS), sorted inside by (low target bits, rpos, y).  Where the word would
+// not fit 63 bits (anchor_word_ybits; the stage then returns 1) the mapper emits no words: it
+// takes its two-key fallback (mm_map.hip sort_anchor_set).
 #include "mm_common.hpp"
 #include "sort.hpp"
 

@@ -1553,7 +1553,7 @@ struct BacktrackParams {
     const int64_t *g_start;
     const int32_t *f;
     const int32_t *p;
-    uint8_t *t;                // marks, one byte per anchor, zeroed by the caller.  Groups are disjoint anchor ranges
+    uint8_t *t;                // marks, one byte per anchor, zeroed by chain_set's fill.  Groups are disjoint anchor ranges
                                // marked by one thread or one wave each, but neighbours share 32-bit words:
                                // byte stores only, never a read-modify-write of a wider word
     const int32_t *z_cnt;      // per group: length of its (f, idx)-ascending z list
@@ -1572,7 +1572,7 @@ struct BacktrackParams {
 // mg_chain_backtrack, one thread per group.  The walk from a start anchor follows p[] once:
 // its path is recorded in chain_ids (this thread's own scratch), so mg_chain_bk_end's t = 2
 // marks and its reset walk are not needed (p[i] < i: a path never revisits itself), and the
-// chain is path[0, best end), left in walk order (end -> start; chain_list / chain_copy read it
+// chain is path[0, best end), left in walk order (end -> start; its readers take it
 // reversed).  Path nodes are marked as the walk passes them and the few past the best end
 // unmarked afterwards, so no pass re-reads the path.  t after the backtrack: 0 = free, 1 = used
 // by a walk whose chain was dropped (score or count below the minimum), 2 = in a kept chain

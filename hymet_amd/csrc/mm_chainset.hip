@@ -106,13 +106,13 @@ __global__ __launch_bounds__(256) void group_heads_write_kernel(const uint32_t *
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) g_start[G] = n;
 }
 
-// x's low words of an anchor set written without them (the two-key, re-sort and test paths)
+// x's low words of an anchor set written without them (the two-key and test paths)
 __global__ void x_low_kernel(const uint64_t *x, int64_t n, uint32_t *x32) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x32[i] = (uint32_t)x[i];
 }
 
-// the head bitmap of an anchor set written without one (the two-key and re-sort paths):
+// the head bitmap of an anchor set written without one (the two-key and test paths):
 // x >> 32 differs from the previous anchor's, a wave's 64 anchors per 64-bit word
 __global__ __launch_bounds__(256) void head_bits_x_kernel(const uint64_t *x, int64_t n, uint64_t *hb) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -136,18 +136,14 @@ __global__ void max_group_kernel(const int64_t *g_start, const int32_t *order, i
     *out = best;
 }
 
-// groups of fewer than min_cnt anchors: f = 0, p = -1, mark t = 0 (the chaining kernels write f
-// and p of the anchors of every work group, so neither needs a pass over the set).  t: byte
-// stores, a neighbouring group's marks share the word; null when the caller keeps no marks
-__global__ void nonwork_fp_kernel(const int64_t *g_start, int32_t G, int min_cnt, int32_t *f, int32_t *p, uint8_t *t) {
+// groups of fewer than min_cnt anchors: f = 0, p = -1 (the chaining kernels write f and p of
+// the anchors of every work group, so neither needs a pass over the set)
+__global__ void nonwork_fp_kernel(const int64_t *g_start, int32_t G, int min_cnt, int32_t *f, int32_t *p) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
     const int64_t a0 = g_start[g], a1 = g_start[g + 1];
     if (a1 - a0 >= min_cnt) return;
-    for (int64_t a = a0; a < a1; a++) {
-        f[a] = 0, p[a] = -1;
-        if (t) t[a] = 0;
-    }
+    for (int64_t a = a0; a < a1; a++) f[a] = 0, p[a] = -1;
 }
 
 // also clears the per-group query-first flags and the z-order list counters
@@ -555,8 +551,8 @@ __global__ void chain_list_kernel(const int64_t *g_start, const int32_t *n_chain
     }
 }
 
-// anchors per chain in the compacted copy; with a long join (qflag), chains of flagged
-// queries are left out of the copy and counted in cnt2 instead (they are only marked)
+// anchors per chain in chain order; with a long join (qflag and cnt2 given), the chains of
+// flagged queries count into cnt2 instead: they take no slots, their anchors are only marked
 __global__ void chain_cnt_kernel(const uint64_t *cu, const uint32_t *cq, const uint32_t *qflag, int64_t n, uint32_t *cnt,
                                  uint32_t *cnt2) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -569,7 +565,7 @@ __global__ void chain_cnt_kernel(const uint64_t *cu, const uint32_t *cq, const u
 
 // long join, first pass (map.c's rmq rescue): a query is re-chained when it has more than one
 // chain and its first chain (compact order) leaves too much of it uncovered -- read from the
-// chain list before the copy
+// chain list
 __global__ void rechain_flag_kernel(const uint32_t *ay, const int32_t *chain_ids, const uint64_t *cu, const int64_t *cfirst,
                                     const int64_t *qc, const int64_t *qlen, int n_q, int rescue_size, float rescue_ratio,
                                     uint32_t *flag) {
@@ -587,68 +583,12 @@ __global__ void rechain_flag_kernel(const uint32_t *ay, const int32_t *chain_ids
     flag[q] = f;
 }
 
-// per-query anchor offsets of a compacted copy: the offset of the query's first chain
+// per-query anchor offsets in chain order: the offset of the query's first chain
 __global__ void chain_qb_kernel(const int64_t *qc, const int64_t *bpos, int64_t n_chain, int64_t nb, int n_q, int64_t *qb) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q > n_q) return;
     const int64_t c = qc[q];
     qb[q] = c < n_chain ? bpos[c] : nb;
-}
-
-// anchors of chain c in start -> end order, and c per anchor (the chains of queries the long
-// join re-chains have no anchors here: cnt 0)
-__global__ __launch_bounds__(256) void chain_copy_kernel(const uint64_t *cu, const int64_t *cfirst, const int64_t *bpos,
-                                                         const int32_t *chain_ids, const uint64_t *ax, const uint32_t *ay,
-                                                         int64_t n_chain, int64_t nb, uint64_t *bx, uint32_t *by,
-                                                         int32_t *bchain) {
-    // flat over the output anchors (~40 B each, bandwidth-bound: C4 copies ~236 M per batch at
-    // ~3.8 TB/s): the block's first chain c0 by binary search over bpos; the starts of the next
-    // 256 chains are staged in LDS and each lane finds its chain by an 8-step search there (a
-    // forward walk per lane cost up to 255 dependent loads where chains are short).  Chains
-    // left out of the copy have no anchors, so more than 256 may start in the block: lanes
-    // past the staged ones search bpos itself.
-    __shared__ int64_t s_c0;
-    __shared__ int32_t s_st[257];  // block-relative starts of chains c0 .. c0 + 256 (clamped)
-    const int64_t b0 = (int64_t)blockIdx.x * blockDim.x;
-    if (threadIdx.x == 0) {
-        int64_t lo = 0, hi = n_chain - 1;  // last c with bpos[c] <= b0
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (bpos[mid] <= b0) lo = mid;
-            else hi = mid - 1;
-        }
-        s_c0 = lo;
-    }
-    __syncthreads();
-    const int64_t c0 = s_c0;
-    for (int i = threadIdx.x; i < 257; i += blockDim.x) {
-        const int64_t c = c0 + i;
-        s_st[i] = c < n_chain ? (int32_t)min(bpos[c] - b0, (int64_t)256) : 256;
-    }
-    __syncthreads();
-    const int64_t b = b0 + threadIdx.x;
-    if (b >= nb) return;
-    int lo = 0, hi = 256;  // last i with s_st[i] <= threadIdx.x (s_st[0] <= 0, nondecreasing)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (s_st[mid] <= (int)threadIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    int64_t c = c0 + lo;
-    if (lo == 256) {  // last c with bpos[c] <= b beyond the staged chains
-        int64_t l2 = c, h2 = n_chain - 1;
-        while (l2 < h2) {
-            const int64_t mid = (l2 + h2 + 1) >> 1;
-            if (bpos[mid] <= b) l2 = mid;
-            else h2 = mid - 1;
-        }
-        c = l2;
-    }
-    const int32_t m = (int32_t)cu[c];
-    const int64_t a = chain_ids[cfirst[c] + m - 1 - (b - bpos[c])];  // backtrack stores end -> start
-    bx[b] = ax[a];
-    by[b] = ay[a];
-    bchain[b] = (int32_t)c;
 }
 
 // Long-join anchors: the first pass's chain anchors (t == 2 after the backtrack) of the
@@ -905,15 +845,14 @@ static int build_work_list(hymet_ctx *ctx, const Groups &Gr, int min_cnt, WorkLi
 // f / p of every anchor: the chaining kernels write those of the work groups; the anchors of
 // groups of fewer than min_cnt anchors get f = 0, p = -1 from nonwork_fp_kernel instead of
 // memsets of all n.  The walk's stamps go to the context's stamp scratch (zero before and
-// after); mark: the backtrack's byte marks (zeroed by the caller), or none
+// after)
 static int chain_dp(hymet_ctx *ctx, const DpArgs &a, const AnchorSet &A, const Groups &Gr, const WorkList &W, DevBuf &f,
-                    DevBuf &p, uint8_t *mark) {
+                    DevBuf &p) {
     HY_HIP(f.alloc(4 * (size_t)A.n, ctx->stream));
     HY_HIP(p.alloc(4 * (size_t)A.n, ctx->stream));
     int32_t *stamp = nullptr;
     HY_HIP(stamp_scratch(ctx, A.n, &stamp));
-    LAUNCH1(nonwork_fp_kernel, Gr.G, Gr.g_start.as<int64_t>(), (int32_t)Gr.G, a.min_cnt, f.as<int32_t>(), p.as<int32_t>(),
-            mark);
+    LAUNCH1(nonwork_fp_kernel, Gr.G, Gr.g_start.as<int64_t>(), (int32_t)Gr.G, a.min_cnt, f.as<int32_t>(), p.as<int32_t>());
     return launch_chain(ctx, A.ax32.as<int32_t>(), A.ay.as<uint32_t>(), A.span, Gr.g_start.as<int64_t>(), Gr.qfirst.as<uint8_t>(),
                         W.order.as<int32_t>(), (int32_t)W.n_work, f.as<int32_t>(), p.as<int32_t>(), stamp, a.max_dist,
                         a.max_dist_inner, a.bw, a.max_chn_skip, a.cap_rmq_size, a.pen_gap, a.pen_skip, A.n, Gr.G);
@@ -1037,44 +976,32 @@ static int chain_list(hymet_ctx *ctx, const AnchorSet &A, int n_q, const Groups 
     return HYMET_OK;
 }
 
-// Where every chain's anchors go in chain order (C.cboff, C.d_qb; with `copy` the anchors
-// themselves: the re-sort / two-key long-join paths read them as a copy), and the long join's
-// hand-over: the re-chained queries (lj->flag) from the chain list; with mark_only their
-// chains take no slots, and their anchor counts (lj->qb2, lj->n2) and the backtrack's marks t
-// (lj->mark) go to the long join instead
+// Where every chain's anchors go in chain order (C.cboff, C.d_qb), and the long join's
+// hand-over: the re-chained queries (lj->flag) from the chain list; their chains take no
+// slots, and their anchor counts (lj->qb2, lj->n2) and the backtrack's marks t (lj->mark) go
+// to the long join instead
 static int chain_layout(hymet_ctx *ctx, const AnchorSet &A, int n_q, const DevBuf &chain_ids, const DevBuf &cfirst,
-                        ChainSet &C, LeanJoin *lj, bool copy, DevBuf &t) {
+                        ChainSet &C, LeanJoin *lj, DevBuf &t) {
     const int64_t NC = C.n_chain;
-    const uint32_t *qflag = nullptr;
+    DevBuf ccnt, ccnt2;
+    HY_HIP(ccnt.alloc(4 * (size_t)(NC + 1), ctx->stream));
     if (lj) {
         HY_HIP(lj->flag.alloc(4 * (size_t)n_q, ctx->stream));
         LAUNCH1(rechain_flag_kernel, n_q, A.ay.as<uint32_t>(), chain_ids.as<int32_t>(), C.cu.as<uint64_t>(),
                 cfirst.as<int64_t>(), C.d_qc.as<int64_t>(), lj->qlen, n_q, lj->rescue_size, lj->rescue_ratio,
                 lj->flag.as<uint32_t>());
-        if (lj->mark_only) qflag = lj->flag.as<uint32_t>();
+        HY_HIP(ccnt2.alloc(4 * (size_t)(NC + 1), ctx->stream));
     }
-    // anchors of every chain (but those only marked), compacted in chain order
-    DevBuf ccnt, ccnt2;
-    HY_HIP(ccnt.alloc(4 * (size_t)(NC + 1), ctx->stream));
-    if (qflag) HY_HIP(ccnt2.alloc(4 * (size_t)(NC + 1), ctx->stream));
-    LAUNCH1(chain_cnt_kernel, NC, C.cu.as<uint64_t>(), C.cq.as<uint32_t>(), qflag, NC, ccnt.as<uint32_t>(),
-            qflag ? ccnt2.as<uint32_t>() : nullptr);
+    // anchors of every chain (but those only marked) in chain order
+    LAUNCH1(chain_cnt_kernel, NC, C.cu.as<uint64_t>(), C.cq.as<uint32_t>(), lj ? lj->flag.as<uint32_t>() : nullptr, NC,
+            ccnt.as<uint32_t>(), lj ? ccnt2.as<uint32_t>() : nullptr);
     int64_t NB = 0;
     int rc = scan_flags(ctx, ccnt.as<uint32_t>(), NC, C.cboff, &NB);
     if (rc) return rc;
     C.n_anchor = NB;
-    if (copy) {
-        HY_HIP(C.bx.alloc(8 * (size_t)(NB + 1), ctx->stream));
-        HY_HIP(C.by.alloc(4 * (size_t)(NB + 1), ctx->stream));
-        HY_HIP(C.bchain.alloc(4 * (size_t)(NB + 1), ctx->stream));
-        if (NC > 0 && NB > 0)
-            LAUNCH1(chain_copy_kernel, NB, C.cu.as<uint64_t>(), cfirst.as<int64_t>(), C.cboff.as<int64_t>(),
-                    chain_ids.as<int32_t>(), A.ax.as<uint64_t>(), A.ay.as<uint32_t>(), NC, NB, C.bx.as<uint64_t>(),
-                    C.by.as<uint32_t>(), C.bchain.as<int32_t>());
-    }
     HY_HIP(C.d_qb.alloc(8 * (size_t)(n_q + 1), ctx->stream));
     LAUNCH1(chain_qb_kernel, n_q + 1, C.d_qc.as<int64_t>(), C.cboff.as<int64_t>(), NC, NB, n_q, C.d_qb.as<int64_t>());
-    if (qflag) {
+    if (lj) {
         DevBuf boff2;
         rc = scan_flags(ctx, ccnt2.as<uint32_t>(), NC, boff2, &lj->n2);
         if (rc) return rc;
@@ -1090,7 +1017,7 @@ static int chain_layout(hymet_ctx *ctx, const AnchorSet &A, int n_q, const DevBu
 }  // namespace
 
 int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_skip, int bw, AnchorSet &A, int n_q,
-              ChainSet &C, LeanJoin *lj, bool copy) {
+              ChainSet &C, LeanJoin *lj) {
     const int64_t n = A.n;
     HY_ARG(n >= 0 && n < INT32_MAX, "chain_set: an anchor set of 2^31 anchors or more (32-bit chain links)");
     C.ax = A.ax.as<uint64_t>(), C.ay = A.ay.as<uint32_t>(), C.span = A.span;
@@ -1122,7 +1049,7 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
                 (long long)W.n_work, (long long)W.largest);
     DevBuf f, p;
     rc = chain_dp(ctx, DpArgs{opt->max_gap, opt->rmq_inner_dist, bw, opt->max_chain_skip, opt->rmq_size_cap, pen_gap, pen_skip,
-                              opt->min_cnt}, A, Gr, W, f, p, t.as<uint8_t>());
+                              opt->min_cnt}, A, Gr, W, f, p);
     if (rc) return rc;
     ZOrder Z;
     rc = z_order(ctx, opt->min_chain_score, f, n, Gr, W, Z);
@@ -1133,7 +1060,7 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
     DevBuf cfirst;
     rc = chain_list(ctx, A, n_q, Gr, B, C, cfirst);
     if (rc) return rc;
-    rc = chain_layout(ctx, A, n_q, B.ids, cfirst, C, lj, copy, t);
+    rc = chain_layout(ctx, A, n_q, B.ids, cfirst, C, lj, t);
     if (rc) return rc;
     // regions and chain statistics read the chains in place
     C.ids.swap(B.ids);
@@ -1225,9 +1152,8 @@ extern "C" int hymet_mm_chain_dp(hymet_ctx *ctx, const uint64_t *h_x, const uint
     WorkList W;
     rc = build_work_list(ctx, Gr, 1, W);
     if (rc) return rc;
-    DevBuf f, p;  // (no marks: the stamps are the context's, as for every caller)
-    rc = chain_dp(ctx, DpArgs{max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, pen_gap, pen_skip, 1}, A, Gr, W, f, p,
-                  nullptr);
+    DevBuf f, p;  // (the stamps are the context's, as for every caller)
+    rc = chain_dp(ctx, DpArgs{max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, pen_gap, pen_skip, 1}, A, Gr, W, f, p);
     if (rc) return rc;
     HY_HIP(hipMemcpyAsync(h_f, f.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     std::vector<int32_t> p32((size_t)n);  // the links are 32-bit on the device: widened for the caller

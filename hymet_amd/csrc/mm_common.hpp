@@ -156,8 +156,8 @@ int inclusive_max_scan_i32(hymet_ctx *ctx, const int32_t *in, int32_t *out, int6
 // An anchor on its way to the grouped sort is one word, W = (rev << (rb + pb) | rid << pb | rpos)
 // << ybits | y: its order inside a query (the query comes from the offsets, the span in y's
 // high word is the batch's constant).  -> ybits for queries up to max_qlen, or 0 where the
-// word would pass 63 bits (all-ones is the sorts' padding) and the key / value pair with the
-// device sort is used instead.
+// word would pass 63 bits (all-ones is the sorts' padding) and the mapper takes its two-key
+// fallback instead.
 inline int anchor_word_ybits(int rb, int pb, int64_t max_qlen) {
     int yb = 1;
     while (yb <= 32 && (1ll << yb) <= max_qlen) yb++;

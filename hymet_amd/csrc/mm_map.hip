@@ -10,16 +10,18 @@
 //   4 anchors: exclusive scan of seed occurrence counts, one thread per seed writes them
 //   5 sort anchors by (query, strand, target, tpos, qpos): the grouped per-query sort of
 //     mm_asort.hip (block sorts in LDS; the library's LSD radix sort only for groups of
-//     more than 16384 anchors)
+//     more than 16384 anchors); a layout without an anchor word takes the two-key fallback
 //   6 chain_set (mm_chainset.hip): groups (query, strand, target) -> chain_groups_kernel (one
 //     wave per group) -> backtrack_groups_kernel -> chains ordered by first anchor (compact_a)
-//   7 long-join re-chain of the chained anchors with bw_long for the queries that need it
+//   7 long-join re-chain with bw_long for the queries that need it: their chained anchors,
+//     compacted out of the sorted first-pass set by the backtrack's marks
 //   8 one thread per query: mm_gen_regs, mm_set_parent, mm_select_sub, mm_est_err,
 //     mm_filter_strand_retained, mm_set_mapq
 // Canonical tie-breaks T1-T4 are those of oracle/mm_oracle.c.
 #include "mm_stages.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -367,12 +369,11 @@ __global__ void write_anchors_kernel(AnchorParams P) {
     }
 }
 
-// Anchor keys (the default path): one 64-bit word per anchor packing exactly its sort order
+// Anchor words (the default path): one 64-bit word per anchor packing exactly its sort order
 // inside its query -- W = (rev | rid | rpos) << ybits | y's low word, field widths from the
 // batch (index sequences, longest index sequence, longest query; anchor_word_ybits) -- for
-// the grouped sort, which takes the query from the anchor offsets.  Where that sort is off
-// or the word does not fit (ybits == 0): the key K = q | rev | rid | rpos, exactly the sort
-// order of (query, x), and the low 32 bits of y as a value of its own, for the device sort.
+// the grouped sort, which takes the query from the anchor offsets.  A layout without a word
+// (ybits == 0) takes write_anchors_kernel and the two-key sort instead.
 // The high bits of y hold the span, which is k for every minimizer of a non-HPC sketch.  One
 // block per 256 consecutive minimizers: the block stages their anchor offsets, position-list
 // starts and query coordinates in LDS, then its 256 lanes sweep the block's anchors
@@ -389,9 +390,8 @@ struct AnchorKeyParams {
     const uint64_t *ipos;
     int64_t n;                // minimizers
     int rb, pb;               // bits for rid / rpos
-    int ybits;                // > 0: words (no val)
+    int ybits;                // bits for y's low word (> 0)
     uint64_t *key;
-    uint32_t *val;
     const int64_t *mp_pos;
     uint64_t *mini_pos;
 };
@@ -400,7 +400,6 @@ __global__ __launch_bounds__(256) void write_anchor_keys_kernel(AnchorKeyParams 
     __shared__ int64_t s_a[257];
     __shared__ uint64_t s_r[256];   // start of the minimizer's position list
     __shared__ uint32_t s_yf[256], s_yr[256], s_strand[256];
-    __shared__ uint64_t s_q[256];   // q << (1 + rb + pb)
     const int tid = threadIdx.x;
     const int64_t m0 = (int64_t)blockIdx.x * 256;
     const int cnt = (int)min((int64_t)256, P.n - m0);
@@ -416,7 +415,6 @@ __global__ __launch_bounds__(256) void write_anchor_keys_kernel(AnchorKeyParams 
         s_yf[tid] = q_pos >> 1;
         s_yr[tid] = (uint32_t)((int32_t)P.qlen[q] - (int32_t)((q_pos >> 1) + 1 - q_span) - 1);
         s_strand[tid] = q_pos & 1;
-        s_q[tid] = (uint64_t)q << (1 + P.rb + P.pb);
     }
     if (tid == 0) s_a[cnt] = P.a_pos[m0 + cnt];
     __syncthreads();
@@ -435,41 +433,7 @@ __global__ __launch_bounds__(256) void write_anchor_keys_kernel(AnchorKeyParams 
         const uint32_t rev = ((uint32_t)rk & 1) != s_strand[lo];
         const uint64_t k = (uint64_t)rev << sh_rev | rid << P.pb | rpos;
         const uint32_t y = rev ? s_yr[lo] : s_yf[lo];
-        if (P.ybits) {
-            P.key[a] = k << P.ybits | y;
-        } else {
-            P.key[a] = s_q[lo] | k;
-            P.val[a] = y;
-        }
-    }
-}
-
-// sorted keys -> (x, y); runs of equal key (one query minimizer position hit by several
-// query minimizers) are ordered by y here: the lane at a run's start writes the run's y
-// values by insertion sort (runs are short and rare), the other lanes of the run skip y.
-__global__ void anchor_unpack_kernel(const uint64_t *key, const uint32_t *val, int64_t n, int rb, int pb, uint64_t *ax,
-                                     uint32_t *ay) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t k = key[i];
-    const uint64_t rev = k >> (rb + pb) & 1, rid = k >> pb & ((1ull << rb) - 1), rpos = k & ((1ull << pb) - 1);
-    ax[i] = rev << 63 | rid << 32 | rpos;
-    const bool prev_eq = i > 0 && key[i - 1] == k;
-    const bool next_eq = i + 1 < n && key[i + 1] == k;
-    if (!prev_eq && !next_eq) {
-        ay[i] = val[i];
-    } else if (!prev_eq) {
-        int64_t e = i + 1;
-        while (e + 1 < n && key[e + 1] == k) e++;
-        for (int64_t a = i; a <= e; a++) {
-            const uint32_t v = val[a];
-            int64_t b = a;
-            while (b > i && ay[b - 1] > v) {
-                ay[b] = ay[b - 1];
-                b--;
-            }
-            ay[b] = v;
-        }
+        P.key[a] = k << P.ybits | y;
     }
 }
 
@@ -504,49 +468,6 @@ __global__ void mini_base_kernel(const uint64_t *my, const uint32_t *seed_n, con
     const int64_t b = qbase[q] + ((uint32_t)my[i] >> 1);
     const uint64_t bits = tab[b >> 6].bits;
     tab[b >> 6].base = (uint32_t)(mp_pos[i] - mp_pos[qm_off[q]]) - (uint32_t)__popcll(bits & ((1ull << (b & 63)) - 1));
-}
-
-// re-chain input: the chained anchors of flagged queries (query-major), with sort keys
-__global__ void rechain_gather_kernel(const uint64_t *bx, const uint32_t *by, const int64_t *qb, const uint32_t *qflag,
-                                      const int64_t *new_off, int n_q, int rb, uint64_t *x, uint32_t *y, uint64_t *k1,
-                                      uint64_t *k2, uint32_t *val) {
-    const int q = blockIdx.x;
-    if (q >= n_q || !qflag[q]) return;
-    const int64_t b0 = qb[q], b1 = qb[q + 1], o = new_off[q];
-    for (int64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x) {
-        const int64_t a = o + (i - b0);
-        const uint64_t ax = bx[i];
-        const uint32_t ay = by[i];
-        x[a] = ax;
-        y[a] = ay;
-        k1[a] = (uint64_t)q << (1 + rb) | (ax >> 63) << rb | (ax << 1 >> 33);
-        k2[a] = (uint64_t)(uint32_t)ax << 32 | ay;
-        val[a] = (uint32_t)a;
-    }
-}
-
-// one thread per re-chain anchor (flat: a block per query left the long queries' blocks as
-// the tail); the block's first query by one binary search, each lane's by a short forward walk
-__global__ __launch_bounds__(256) void rechain_keys_kernel(const uint64_t *bx, const uint32_t *by, const int64_t *qb,
-                                                           const int64_t *new_off, int n_q, int64_t n, int rb, int pb,
-                                                           int ybits, uint64_t *key, uint32_t *val) {
-    __shared__ int s_q0;
-    const int64_t a0 = (int64_t)blockIdx.x * blockDim.x;
-    if (threadIdx.x == 0) s_q0 = upper_idx(new_off, n_q, a0);
-    __syncthreads();
-    const int64_t a = a0 + threadIdx.x;
-    if (a >= n) return;
-    int q = s_q0;
-    while (q + 1 < n_q && new_off[q + 1] <= a) q++;  // last q with new_off[q] <= a
-    const int64_t i = qb[q] + (a - new_off[q]);
-    const uint64_t ax = bx[i];
-    const uint64_t k = (ax >> 63) << (rb + pb) | (ax << 1 >> 33) << pb | (uint32_t)ax;
-    if (ybits) {  // words, as write_anchor_keys_kernel's
-        key[a] = k << ybits | by[i];
-    } else {
-        key[a] = (uint64_t)q << (1 + rb + pb) | k;
-        val[a] = by[i];
-    }
 }
 
 // per query: regions kept (first-pass chains, or the long-join re-chain's for flagged queries)
@@ -614,7 +535,9 @@ struct PhaseTrace {
     }
 };
 
-// sort raw anchors (x, y's low word, k1 with k2 keys) into an AnchorSet
+// the two-key fallback (layouts without a word, HYMET_ANCHOR_LEGACY=1): sort raw anchors (x,
+// y's low word, k1 with k2 keys) into an AnchorSet -- by (tpos, qpos), then stably by (query,
+// strand, target) -- through a permutation, with the library's LSD radix sort
 static int sort_anchor_set(hymet_ctx *ctx, DevBuf &x, DevBuf &y, DevBuf &k1, DevBuf &k2, DevBuf &val, int64_t n,
                            int key1_bits, int yhi, AnchorSet &out) {
     DevBuf k2b, valb, k1g, k1b;
@@ -639,8 +562,8 @@ static int sort_anchor_set(hymet_ctx *ctx, DevBuf &x, DevBuf &y, DevBuf &k1, Dev
     return HYMET_OK;
 }
 
-// sort anchor words (write_anchor_keys_kernel / rechain_keys_kernel with ybits > 0) into an
-// AnchorSet: the per-query grouped sort (mm_asort.hip), which writes (x, y) itself
+// sort anchor words (write_anchor_keys_kernel) into an AnchorSet: the per-query grouped sort
+// (mm_asort.hip), which writes (x, y) itself
 static int sort_anchor_words(hymet_ctx *ctx, DevBuf &word, int64_t n, int rb, int pb, int yhi, const int64_t *d_qoff, int n_q,
                              int64_t max_qlen, AnchorSet &out) {
     DevBuf wb;
@@ -677,37 +600,13 @@ static int sort_anchor_words(hymet_ctx *ctx, DevBuf &word, int64_t n, int rb, in
     return HYMET_OK;
 }
 
-// sort anchor keys (write_anchor_keys_kernel / rechain_keys_kernel with ybits == 0: the
-// grouped sort is off, HYMET_ANCHOR_GSORT=0, or has no word for the layout) into an AnchorSet:
-// one LSD radix sort over the key's significant bits, then unpack to (x, y)
-static int sort_anchor_keys(hymet_ctx *ctx, DevBuf &key, DevBuf &val, int64_t n, int end_bit, int rb, int pb, int yhi,
-                            AnchorSet &out) {
-    DevBuf kb, vb;
-    HY_HIP(kb.alloc(8 * (size_t)n, ctx->stream));
-    HY_HIP(vb.alloc(4 * (size_t)n, ctx->stream));
-    HY_HIP(out.ax.alloc(8 * (size_t)n, ctx->stream));
-    HY_HIP(out.ay.alloc(4 * (size_t)n, ctx->stream));
-    out.n = n;
-    out.span = yhi & 0xff;
-    uint64_t *kk = key.as<uint64_t>(), *kka = kb.as<uint64_t>();
-    uint32_t *vv = val.as<uint32_t>(), *vva = vb.as<uint32_t>();
-    int rc = sort_pairs<uint64_t, uint32_t>(ctx, kk, kka, vv, vva, n, 0, end_bit, "radix_sort_anchors");
-    if (rc) return rc;
-    {
-        ProfScope _ps(ctx, "mm_anchor_unpack", 24.0 * (double)n);  // key + value read, x + y (4 B) write
-        LAUNCH1(anchor_unpack_kernel, n, kk, vv, n, rb, pb, out.ax.as<uint64_t>(), out.ay.as<uint32_t>());
-    }
-    return HYMET_OK;
-}
-
 // HYMET_DUMP_ANCHORS=path (profiling, tools/chain_prof): the first call's sorted first-pass
 // anchors as (x, y) pairs with x>>32 replaced by the (query, strand, target) group ordinal;
 // HYMET_DUMP_ANCHORS2=path: the same for the long-join re-chain's anchors.  `dumped`: the
-// variable's one dump of the process has been written.
-static int dump_anchors(hymet_ctx *ctx, const char *var, const AnchorSet &S, int n_q, bool &dumped) {
+// variable's one dump of the process has been claimed (the mapping threads share the flag).
+static int dump_anchors(hymet_ctx *ctx, const char *var, const AnchorSet &S, int n_q, std::atomic<bool> &dumped) {
     const char *path = env_str(var);
-    if (!path || dumped || S.n == 0) return HYMET_OK;
-    dumped = true;
+    if (!path || S.n == 0 || dumped.exchange(true)) return HYMET_OK;
     hipStream_t st = ctx->stream;
     const int64_t nd = std::min<int64_t>(S.n, env_int("HYMET_DUMP_MAX", 1 << 24, 0, INT64_MAX));  // anchors to dump
     std::vector<uint64_t> hx(nd);
@@ -791,11 +690,6 @@ struct MapBatch {
     DevBuf d_qbase, pos_tab;
     std::vector<int64_t> qbase;  // lives until the call returns (async H2D source)
     int64_t max_qlen = 1;
-    // the anchor sort key: bits of the target id and position, of (query, strand, target), and
-    // whether (query, strand, rid, rpos) fits one 64-bit key
-    int rb = 0, pb = 0, key1_bits = 0;
-    bool key_path = false;
-    int ybits = 0;  // > 0: the key path emits anchor words for the grouped sort (anchor_word_ybits)
 };
 
 // 1 sketch: the queries' minimizers, lengths and name hashes on the device
@@ -1000,37 +894,33 @@ static int first_pass_anchors(MapBatch &B, AnchorSet &S1) {
     hipLaunchKernelGGL(sample_off_kernel, dim3((unsigned)cdiv(n_q + 1, 256)), dim3(256), 0, st, a_pos.as<int64_t>(),
                        qm_off.as<int64_t>(), n_q, A, S1.d_off.as<int64_t>());
     HY_CHECK_LAUNCH("sample_off_kernel");
-    B.rb = bits_for(idx->n_seq);
-    B.key1_bits = bits_for(n_q) + 1 + B.rb;
-    HY_ARG(B.key1_bits <= 64, "hymet_mm_map: too many queries x targets for the sort key");
+    // the sort key's fields: bits of the target id and position, of (query, strand, target)
+    const int rb = bits_for(idx->n_seq), key1_bits = bits_for(n_q) + 1 + rb;
+    HY_ARG(key1_bits <= 64, "hymet_mm_map: too many queries x targets for the sort key");
     int64_t max_len = 1;
     for (int64_t l : idx->h_len) max_len = std::max(max_len, l);
-    B.pb = bits_for(max_len - 1);
-    // one-key anchor sort when (query, strand, rid, rpos) fits 64 bits (always, short of
-    // ~2^20 queries per batch against chromosome-scale targets); else the two-key path
-    B.key_path = B.key1_bits + B.pb <= 64 && !env_flag("HYMET_ANCHOR_LEGACY");
-    // anchors as words for the grouped sort where it is on and has a word for this batch's layout
-    B.ybits = B.key_path && env_flag("HYMET_ANCHOR_GSORT", true) ? anchor_word_ybits(B.rb, B.pb, B.max_qlen) : 0;
-    if (B.key_path) {
-        const bool words = B.ybits > 0 && A > 0;
-        DevBuf key, val;
-        HY_HIP(key.alloc(8 * (size_t)(A + 1), st));
-        if (!words) HY_HIP(val.alloc(4 * (size_t)(A + 1), st));
+    const int pb = bits_for(max_len - 1);
+    if (A == 0) {  // no seed at all: the empty set (n = 0, offsets all zero) on either path
+        S1.span = idx->k & 0xff;
+        return HYMET_OK;
+    }
+    // anchors as words for the grouped sort where the batch's layout has one (rb + pb <= 38
+    // with queries below 16 Mbp); else the two-key path
+    const int ybits = env_flag("HYMET_ANCHOR_LEGACY") ? 0 : anchor_word_ybits(rb, pb, B.max_qlen);
+    if (ybits > 0) {
+        DevBuf word;
+        HY_HIP(word.alloc(8 * (size_t)(A + 1), st));
         AnchorKeyParams P{mx.as<uint64_t>(), my.as<uint64_t>(), seed_n.as<uint32_t>(), a_pos.as<int64_t>(),
-                          qid.as<uint32_t>(), d_qlen.as<int64_t>(), idx->d_koff, idx->d_pos, M, B.rb, B.pb,
-                          words ? B.ybits : 0, key.as<uint64_t>(), val.as<uint32_t>(), mp_pos.as<int64_t>(),
-                          B.mini_pos.as<uint64_t>()};
+                          qid.as<uint32_t>(), d_qlen.as<int64_t>(), idx->d_koff, idx->d_pos, M, rb, pb,
+                          ybits, word.as<uint64_t>(), mp_pos.as<int64_t>(), B.mini_pos.as<uint64_t>()};
         {
-            // position fetch + key/value write; the benchmark counts anchors as this scope's bytes
+            // position fetch + word write; the benchmark counts anchors as this scope's bytes
             // / 20, so the constant stays though a word is 8 B where a key and its value were 12
             ProfScope _ps(ctx, "mm_anchors", (double)A * (8.0 + 12.0));
-            if (M > 0) {
-                hipLaunchKernelGGL(write_anchor_keys_kernel, dim3((unsigned)cdiv(M, 256)), dim3(256), 0, st, P);
-                HY_CHECK_LAUNCH("write_anchor_keys_kernel");
-            }
+            hipLaunchKernelGGL(write_anchor_keys_kernel, dim3((unsigned)cdiv(M, 256)), dim3(256), 0, st, P);
+            HY_CHECK_LAUNCH("write_anchor_keys_kernel");
         }
-        if (words) return sort_anchor_words(ctx, key, A, B.rb, B.pb, idx->k, S1.d_off.as<int64_t>(), n_q, B.max_qlen, S1);
-        return sort_anchor_keys(ctx, key, val, A, B.key1_bits + B.pb, B.rb, B.pb, idx->k, S1);
+        return sort_anchor_words(ctx, word, A, rb, pb, idx->k, S1.d_off.as<int64_t>(), n_q, B.max_qlen, S1);
     }
     DevBuf x, y, k1, k2, val;
     HY_HIP(x.alloc(8 * (size_t)(A + 1), st));
@@ -1039,61 +929,37 @@ static int first_pass_anchors(MapBatch &B, AnchorSet &S1) {
     HY_HIP(k2.alloc(8 * (size_t)(A + 1), st));
     HY_HIP(val.alloc(4 * (size_t)(A + 1), st));
     AnchorParams P{mx.as<uint64_t>(), my.as<uint64_t>(), seed_n.as<uint32_t>(), a_pos.as<int64_t>(), qid.as<uint32_t>(),
-                   d_qlen.as<int64_t>(), idx->d_koff, idx->d_pos, M, B.rb, x.as<uint64_t>(), k1.as<uint64_t>(),
+                   d_qlen.as<int64_t>(), idx->d_koff, idx->d_pos, M, rb, x.as<uint64_t>(), k1.as<uint64_t>(),
                    k2.as<uint64_t>(), y.as<uint32_t>(), val.as<uint32_t>(), mp_pos.as<int64_t>(), B.mini_pos.as<uint64_t>()};
     ProfScope _ps(ctx, "mm_anchors", (double)A * (8.0 + 36.0));  // position fetch + anchor/key writes
     LAUNCH1(write_anchors_kernel, M, P);
-    return sort_anchor_set(ctx, x, y, k1, k2, val, A, B.key1_bits, idx->k, S1);
+    return sort_anchor_set(ctx, x, y, k1, k2, val, A, key1_bits, idx->k, S1);
 }
 
 // 7 long join, its anchor set: the chain anchors of the queries the first pass flagged
-// (`flag`), query-major and sorted, into S2; any: some query is flagged
-static int long_join_anchors(MapBatch &B, const AnchorSet &S1, const ChainSet &C1, const LeanJoin &lj, const DevBuf &flag,
-                             AnchorSet &S2, bool &any) {
+// (`flag`), compacted out of the first-pass set S1 -- which keeps its (query, x, y) order --
+// into S2; any: some query is flagged
+static int long_join_anchors(MapBatch &B, const AnchorSet &S1, const LeanJoin &lj, const DevBuf &flag, AnchorSet &S2,
+                             bool &any) {
     hymet_ctx *ctx = B.ctx;
-    hipStream_t st = ctx->stream;
     const int n_q = B.n_q;
     // anchors of flagged queries only: their per-query offsets, built on the device (the
     // total and whether any query is flagged come back through the mailbox)
-    const DevBuf &qbuf = lj.mark_only ? lj.qb2 : C1.d_qb;
     DevBuf fcnt;
-    HY_HIP(fcnt.alloc(4 * (size_t)(n_q + 1), st));
+    HY_HIP(fcnt.alloc(4 * (size_t)(n_q + 1), ctx->stream));
     ctx->mbox_h[kMbFlag] = 0;
-    LAUNCH1(flagged_len_kernel, n_q + 1, flag.as<uint32_t>(), qbuf.as<int64_t>(), n_q, fcnt.as<uint32_t>(), mb_dev(ctx, kMbFlag));
+    LAUNCH1(flagged_len_kernel, n_q + 1, flag.as<uint32_t>(), lj.qb2.as<int64_t>(), n_q, fcnt.as<uint32_t>(),
+            mb_dev(ctx, kMbFlag));
     int64_t A2 = 0;
     int rc = scan_flags(ctx, fcnt.as<uint32_t>(), n_q + 1, S2.d_off, &A2);  // (syncs the stream)
     if (rc) return rc;
     any = mb_read(ctx, kMbFlag) != 0;
     if (!any) return HYMET_OK;
     HY_ARG(A2 <= anchor_cap(), "hymet_mm_map: the long join has more anchors than 32-bit chain links hold");
-    if (lj.mark_only) {
-        // the flagged queries' chain anchors (t == 2 from the backtrack), compacted out of
-        // the first-pass set in its (key, y) order -- already the long join's sorted set
-        rc = marked_anchor_set(ctx, S1, lj, flag.as<uint32_t>(), n_q, A2, S2);
-    } else if (B.key_path) {
-        const bool words = B.ybits > 0 && A2 > 0;
-        DevBuf key, val;
-        HY_HIP(key.alloc(8 * (size_t)(A2 + 1), st));
-        if (!words) HY_HIP(val.alloc(4 * (size_t)(A2 + 1), st));
-        LAUNCH1(rechain_keys_kernel, A2, C1.bx.as<uint64_t>(), C1.by.as<uint32_t>(), C1.d_qb.as<int64_t>(),
-                S2.d_off.as<int64_t>(), n_q, A2, B.rb, B.pb, words ? B.ybits : 0, key.as<uint64_t>(), val.as<uint32_t>());
-        rc = words ? sort_anchor_words(ctx, key, A2, B.rb, B.pb, B.idx->k, S2.d_off.as<int64_t>(), n_q, B.max_qlen, S2)
-                   : sort_anchor_keys(ctx, key, val, A2, B.key1_bits + B.pb, B.rb, B.pb, B.idx->k, S2);
-    } else {
-        DevBuf x, y, k1, k2, val;
-        HY_HIP(x.alloc(8 * (size_t)(A2 + 1), st));
-        HY_HIP(y.alloc(4 * (size_t)(A2 + 1), st));
-        HY_HIP(k1.alloc(8 * (size_t)(A2 + 1), st));
-        HY_HIP(k2.alloc(8 * (size_t)(A2 + 1), st));
-        HY_HIP(val.alloc(4 * (size_t)(A2 + 1), st));
-        hipLaunchKernelGGL(rechain_gather_kernel, dim3((unsigned)n_q), dim3(256), 0, st, C1.bx.as<uint64_t>(),
-                           C1.by.as<uint32_t>(), C1.d_qb.as<int64_t>(), flag.as<uint32_t>(), S2.d_off.as<int64_t>(), n_q,
-                           B.rb, x.as<uint64_t>(), y.as<uint32_t>(), k1.as<uint64_t>(), k2.as<uint64_t>(), val.as<uint32_t>());
-        HY_CHECK_LAUNCH("rechain_gather_kernel");
-        rc = sort_anchor_set(ctx, x, y, k1, k2, val, A2, B.key1_bits, S1.span, S2);
-    }
+    // their chain anchors carry mark 2 from the backtrack
+    rc = marked_anchor_set(ctx, S1, lj, flag.as<uint32_t>(), n_q, A2, S2);
     if (rc) return rc;
-    static bool dumped = false;
+    static std::atomic<bool> dumped{false};
     return dump_anchors(ctx, "HYMET_DUMP_ANCHORS2", S2, n_q, dumped);
 }
 
@@ -1201,15 +1067,14 @@ static int mm_map_impl(hymet_ctx *ctx, const hymet_mm_index *idx, const hymet_mm
     rc = first_pass_anchors(B, S1);
     if (rc) return rc;
     tr.mark("anchors+sort");
-    static bool dumped1 = false;
+    static std::atomic<bool> dumped1{false};
     rc = dump_anchors(ctx, "HYMET_DUMP_ANCHORS", S1, n_q, dumped1);
     if (rc) return rc;
     // ------------------------------------------------ 6 chain (+ 7 long join)
     ChainSet C1;
     const bool long_join = opt->bw_long > opt->bw;
-    const bool resort = env_flag("HYMET_RECHAIN_SORT");  // tests: the re-sort path
-    LeanJoin lj{B.d_qlen.as<int64_t>(), opt->rmq_rescue_size, opt->rmq_rescue_ratio, B.key_path && !resort};
-    rc = chain_set(ctx, opt, pen_gap, pen_skip, opt->bw, S1, n_q, C1, long_join ? &lj : nullptr, long_join && !lj.mark_only);
+    LeanJoin lj{B.d_qlen.as<int64_t>(), opt->rmq_rescue_size, opt->rmq_rescue_ratio};
+    rc = chain_set(ctx, opt, pen_gap, pen_skip, opt->bw, S1, n_q, C1, long_join ? &lj : nullptr);
     if (rc) return rc;
     tr.mark("chain_set 1");
     ChainSet C2;
@@ -1218,7 +1083,7 @@ static int mm_map_impl(hymet_ctx *ctx, const hymet_mm_index *idx, const hymet_mm
     bool joined = false;
     if (long_join && C1.n_chain > 0) {
         flag.swap(lj.flag);
-        rc = long_join_anchors(B, S1, C1, lj, flag, S2, joined);
+        rc = long_join_anchors(B, S1, lj, flag, S2, joined);
         if (rc) return rc;
         if (joined) {  // flagged queries take C2's chains, the others keep C1's
             rc = chain_set(ctx, opt, pen_gap, pen_skip, opt->bw_long, S2, n_q, C2);

@@ -84,32 +84,31 @@ struct ChainSet {
     const uint64_t *ax = nullptr;  // the chained anchor set (alive as long as the chains)
     const uint32_t *ay = nullptr;
     int span = 0;
-    DevBuf bx, by, bchain;     // a copy of the chained anchors in chain order (only for re-chain paths; by: 4 B)
-    DevBuf cq;                 // query of each chain
+    DevBuf cq;              // query of each chain
     int64_t n_anchor = 0, n_chain = 0;
     DevBuf d_qc, d_qb;  // n_q + 1 chain / chain-order anchor offsets per query
 };
 
 // A first pass followed by the long join (map.c's rmq rescue): chain_set flags the re-chained
-// queries from its chain list; with mark_only their chains are not copied out (their regions
-// are never built) but marked in the chained anchor set, which the long join compacts.
+// queries from its chain list; their chains take no slots in the chain order (their regions
+// are never built) but stay marked in the chained anchor set, which the long join compacts.
 struct LeanJoin {
     const int64_t *qlen;
     int rescue_size;
     float rescue_ratio;
-    bool mark_only;
     DevBuf flag;                 // per query: re-chained
-    DevBuf mark;                 // mark_only: the backtrack's marks, one byte per anchor of the set (+16 bytes
-                                 // for 16-byte loads): 2 = in a kept chain
-    DevBuf qb2;                  // mark_only: n_q + 1 offsets of the re-chained queries' chain anchors
-    int64_t n2 = 0;
+    DevBuf mark;                 // the backtrack's marks, one byte per anchor of the set (+16 bytes for 16-byte
+                                 // loads): 2 = in a kept chain
+    DevBuf qb2;                  // n_q + 1 offsets of the re-chained queries' chain anchors
+    int64_t n2 = 0;              // their total
 };
 
-// chaining + backtrack + compact_a over an anchor set (mm_chainset.hip)
+// chaining + backtrack + compact_a over an anchor set (mm_chainset.hip); with lj, also the
+// long join's hand-over
 int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_skip, int bw, AnchorSet &A, int n_q,
-              ChainSet &C, LeanJoin *lj = nullptr, bool copy = false);
-// mark_only long join: the flagged queries' marked anchors of S1 (A2 of them, S2.d_off set by
-// the caller), compacted in S1's order into S2 with its head bitmap and x low words
+              ChainSet &C, LeanJoin *lj = nullptr);
+// long join: the flagged queries' marked anchors of S1 (A2 of them, S2.d_off set by the
+// caller), compacted in S1's order into S2 with its head bitmap and x low words
 int marked_anchor_set(hymet_ctx *ctx, const AnchorSet &S1, const LeanJoin &lj, const uint32_t *flag, int n_q, int64_t A2,
                       AnchorSet &S2);
 

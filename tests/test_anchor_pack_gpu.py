@@ -6,8 +6,8 @@ tiled query with a group for the device radix sort and two small groups, queries
 thread / wave / block class boundaries and an empty one -- with 2,048 (strand, target) bins
 (the order-preserving scatter), with 4,096 (the atomic ranking) and with coarse bins; a layout
 one bit too wide, which the entry declines; a y beyond its field, which it rejects; and a
-small mapping with the grouped sort on (anchors emitted as words) and off (key / value pairs
-for the device sort), whose region records must not differ.
+small mapping with anchors emitted as words for the grouped sort and through the two-key
+fallback (the path of layouts without a word), whose region records must not differ.
 """
 import ctypes
 
@@ -154,9 +154,9 @@ def test_y_beyond_its_field_is_rejected(gpu):
 
 
 def test_map_with_words_and_with_pairs(gpu, monkeypatch):
-    """One small mapping twice: HYMET_ANCHOR_GSORT unset (anchors emitted as words, grouped
-    sort) and = 0 (key / value pairs, device sort, unpack).  The profiler's scopes say which
-    form ran; the region records are the same."""
+    """One small mapping twice: HYMET_ANCHOR_LEGACY unset (anchors emitted as words, grouped
+    sort) and = 1 (the two-key fallback: raw anchors, two device sorts, gathers).  The
+    profiler's scopes say which form ran; the region records are the same."""
     from hymet_amd import mapper
     from hymet_amd.seqio import DevicePool, from_records
     rng = np.random.default_rng(77)
@@ -174,21 +174,21 @@ def test_map_with_words_and_with_pairs(gpu, monkeypatch):
     out = {}
     gpu.prof(True)
     try:
-        for form, env in (("words", None), ("pairs", "0")):
+        for form, env in (("words", None), ("twokey", "1")):
             if env is None:
-                monkeypatch.delenv("HYMET_ANCHOR_GSORT", raising=False)
+                monkeypatch.delenv("HYMET_ANCHOR_LEGACY", raising=False)
             else:
-                monkeypatch.setenv("HYMET_ANCHOR_GSORT", env)
+                monkeypatch.setenv("HYMET_ANCHOR_LEGACY", env)
             gpu.prof_reset()
             res = mapper.map_part(gpu, part, qpool, opt)
             out[form] = (res, {k for k, v in gpu.prof_table().items() if v[1] > 0})
     finally:
         gpu.prof(False)
-    (rw, sw), (rp, sp) = out["words"], out["pairs"]
-    assert "mm_anchor_gsort" in sw and "mm_anchor_unpack" not in sw
-    assert "mm_anchor_unpack" in sp and "mm_anchor_gsort" not in sp
+    (rw, sw), (rt, st) = out["words"], out["twokey"]
+    assert "mm_anchor_gsort" in sw and "radix_sort_anchor_group" not in sw
+    assert "radix_sort_anchor_group" in st and "mm_anchor_gsort" not in st
     assert (np.diff(rw.off)[:3] > 0).all()   # the three queries cut from the targets map
-    np.testing.assert_array_equal(rw.off, rp.off)
-    np.testing.assert_array_equal(rw.rep_len, rp.rep_len)
+    np.testing.assert_array_equal(rw.off, rt.off)
+    np.testing.assert_array_equal(rw.rep_len, rt.rep_len)
     for f in rw.regs.dtype.names:
-        np.testing.assert_array_equal(rw.regs[f], rp.regs[f], err_msg=f)
+        np.testing.assert_array_equal(rw.regs[f], rt.regs[f], err_msg=f)

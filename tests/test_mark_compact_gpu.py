@@ -10,7 +10,7 @@ group that continues across a tile boundary and one that ends on it, and a whole
 nothing kept between two tiles that keep (the look-back over last_kept).  y comes back
 widened: the device holds its low word and one span per set.  Also: hymet_mm_chain_dp rejects
 y values of two spans and works on the same context afterwards, and a small mapping whose
-long join runs gives the same region records with the grouped sort and with the device sort.
+long join runs gives the same region records with anchor words and with the two-key fallback.
 """
 import ctypes
 
@@ -213,8 +213,8 @@ def test_chain_dp_rejects_two_spans_then_runs(gpu):
 
 def test_map_long_join_with_words_and_with_pairs(gpu, monkeypatch):
     """One small mapping whose long join runs (a query of two target stretches 35 kbp apart:
-    two first-pass chains, each leaving half of it uncovered), with HYMET_ANCHOR_GSORT unset
-    (the grouped sort writes the first-pass set) and = 0 (device sort and unpack): the
+    two first-pass chains, each leaving half of it uncovered), with HYMET_ANCHOR_LEGACY unset
+    (the grouped sort writes the first-pass set) and = 1 (the two-key fallback writes it): the
     compaction hands the long join the same set either way, and the region records agree."""
     from hymet_amd import mapper
     from hymet_amd.seqio import DevicePool, from_records
@@ -234,23 +234,23 @@ def test_map_long_join_with_words_and_with_pairs(gpu, monkeypatch):
     out = {}
     gpu.prof(True)
     try:
-        for form, env in (("words", None), ("pairs", "0")):
+        for form, env in (("words", None), ("twokey", "1")):
             if env is None:
-                monkeypatch.delenv("HYMET_ANCHOR_GSORT", raising=False)
+                monkeypatch.delenv("HYMET_ANCHOR_LEGACY", raising=False)
             else:
-                monkeypatch.setenv("HYMET_ANCHOR_GSORT", env)
+                monkeypatch.setenv("HYMET_ANCHOR_LEGACY", env)
             gpu.prof_reset()
             res = mapper.map_part(gpu, part, qpool, opt)
             out[form] = (res, {k for k, v in gpu.prof_table().items() if v[1] > 0})
     finally:
         gpu.prof(False)
-    (rw, sw), (rp, sp) = out["words"], out["pairs"]
-    assert "mm_anchor_gsort" in sw and "mm_anchor_unpack" not in sw
-    assert "mm_anchor_unpack" in sp and "mm_anchor_gsort" not in sp
-    for s in (sw, sp):   # the long join chained a set of its own
+    (rw, sw), (rt, st) = out["words"], out["twokey"]
+    assert "mm_anchor_gsort" in sw and "radix_sort_anchor_group" not in sw
+    assert "radix_sort_anchor_group" in st and "mm_anchor_gsort" not in st
+    for s in (sw, st):   # the long join chained a set of its own
         assert "mm_chain_long" in s or "mm_chain_long_small" in s
     assert (np.diff(rw.off)[:3] > 0).all()
-    np.testing.assert_array_equal(rw.off, rp.off)
-    np.testing.assert_array_equal(rw.rep_len, rp.rep_len)
+    np.testing.assert_array_equal(rw.off, rt.off)
+    np.testing.assert_array_equal(rw.rep_len, rt.rep_len)
     for f in rw.regs.dtype.names:
-        np.testing.assert_array_equal(rw.regs[f], rp.regs[f], err_msg=f)
+        np.testing.assert_array_equal(rw.regs[f], rt.regs[f], err_msg=f)

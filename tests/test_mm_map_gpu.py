@@ -53,17 +53,20 @@ def _queries(rng, refs):
     return qs
 
 
-@pytest.mark.parametrize("bt_long,legacy,z_runs,resort,zm", [(None, None, None, None, None), ("4", None, None, None, None),
-                                                            (None, "1", "1", None, None), (None, None, "2", None, None),
-                                                            (None, None, None, "1", None), (None, None, None, None, "0,7"),
-                                                            (None, None, None, None, "regions"),
-                                                            (None, None, None, None, "regions_prim1")])
-def test_map_matches_oracle(gpu, monkeypatch, bt_long, legacy, z_runs, resort, zm):
+# (the ids are those the cases had while a fifth parameter, between z_runs and zm, chose the
+# long join's re-sort path: the cases keep their names now that the path is gone)
+@pytest.mark.parametrize("bt_long,legacy,z_runs,zm", [(None, None, None, None), ("4", None, None, None),
+                                                     (None, "1", "1", None), (None, None, "2", None),
+                                                     (None, None, None, "0,7"), (None, None, None, "regions"),
+                                                     (None, None, None, "regions_prim1")],
+                         ids=["None-None-None-None-None", "4-None-None-None-None", "None-1-1-None-None",
+                              "None-None-2-None-None", "None-None-None-None-0,7", "None-None-None-None-regions",
+                              "None-None-None-None-regions_prim1"])
+def test_map_matches_oracle(gpu, monkeypatch, bt_long, legacy, z_runs, zm):
     """bt_long = "4": nearly every chain group takes the wave-per-group backtrack path.
-    legacy = "1": anchors take the two-key sort path (used when the one-key anchor sort key
-    would exceed 64 bits).  z_runs: backtrack-order groups of more ascending runs than this
-    take the sort fallbacks (block bitonic / global radix) instead of the run merge.
-    resort = "1": the long join re-sorts its anchors instead of compacting the first pass's.
+    legacy = "1": anchors take the two-key sort path (the path of layouts without an anchor
+    word).  z_runs: backtrack-order groups of more ascending runs than this take the sort
+    fallbacks (block bitonic / global radix) instead of the run merge.
     zm = "0,7": no merge group is staged in LDS; each is split into units of 7 entries, one
     block per unit (the path of merge groups above 6,144 entries).
     zm = "regions": every query of more than one chain takes the regions wave kernel, and from
@@ -79,8 +82,6 @@ def test_map_matches_oracle(gpu, monkeypatch, bt_long, legacy, z_runs, resort, z
         lds, unit = zm.split(",")
         monkeypatch.setenv("HYMET_ZM_LDS", lds)
         monkeypatch.setenv("HYMET_ZM_UNIT", unit)
-    if resort is not None:
-        monkeypatch.setenv("HYMET_RECHAIN_SORT", resort)
     if bt_long is not None:
         monkeypatch.setenv("HYMET_BT_LONG", bt_long)
     if legacy is not None:
@@ -119,6 +120,27 @@ def test_map_matches_oracle(gpu, monkeypatch, bt_long, legacy, z_runs, resort, z
         assert g_lines == o_lines
         n_mapped += len(gregs) > 0
     assert n_mapped >= 55
+
+
+def test_map_without_anchors(gpu, monkeypatch):
+    """A batch that yields no anchor at all (an empty query and one of N only), through the
+    word path and through the two-key fallback: the call succeeds with no region records."""
+    from hymet_amd import mapper
+    from hymet_amd.seqio import DevicePool, from_records
+    refs = _refs(np.random.default_rng(21))
+    part = mapper.IndexPart(gpu, from_records([(f"NC_{i:06d}.1", "", s) for i, s in enumerate(refs)]))
+    opt = mapper.MapOpt.asm10()
+    opt.resolve_mid_occ(part)
+    qpool = DevicePool(gpu, from_records([("empty", "", b""), ("allN", "", b"N" * 3000)]), DevicePool.ALPHA_MINIMAP2)
+    for legacy in (None, "1"):
+        if legacy is None:
+            monkeypatch.delenv("HYMET_ANCHOR_LEGACY", raising=False)
+        else:
+            monkeypatch.setenv("HYMET_ANCHOR_LEGACY", legacy)
+        res = mapper.map_part(gpu, part, qpool, opt)   # raises unless the call returns 0
+        np.testing.assert_array_equal(res.off, np.zeros(3, np.int64), err_msg=str(legacy))
+        np.testing.assert_array_equal(res.rep_len, np.zeros(2, np.int32), err_msg=str(legacy))
+        assert len(res.regs) == 0, legacy
 
 
 def test_map_many_targets_matches_oracle(gpu):
