@@ -407,7 +407,7 @@ def cmd_sketch(argv: Sequence[str]) -> int:
 
 
 # ------------------------------------------------------------------ dist (mash dist)
-DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [--sparse] [-i] [-l] REF.msh QUERY..."
+DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] REF.msh QUERY..."
 
 
 def dist_args(argv: Sequence[str]):
@@ -422,6 +422,7 @@ def dist_args(argv: Sequence[str]):
     p.add_argument("-v", type=float, default=1.0, dest="max_p")
     p.add_argument("-t", action="store_true", dest="table")
     p.add_argument("--sparse", action="store_true", dest="sparse")
+    p.add_argument("--top", type=int, default=None, dest="top")
     p.add_argument("-i", action="store_true", dest="individual")
     p.add_argument("-l", action="store_true", dest="lists")
     p.add_argument("-h", action="store_true", dest="help")
@@ -441,6 +442,16 @@ def dist_args(argv: Sequence[str]):
             raise ValueError("--sparse needs a distance threshold: give -d D with D < 1")
         if a.sparse and not a.max_dist < 1.0:
             raise ValueError(f"--sparse with -d {a.max_dist:g}: the distance threshold must be below 1")
+        if a.top is not None:
+            from .mashdist import topk_max
+            if a.table:
+                raise ValueError("--top does not go with -t: the table holds every pair")
+            if a.max_p < 1.0:
+                raise ValueError("--top does not go with -v P below 1: a p-value filter after the selection "
+                                 "would return fewer than K")
+            if not 1 <= a.top <= topk_max():
+                raise ValueError(f"--top {a.top}: K must be in 1..{topk_max()}")
+        a.top = a.top or 0
         if a.max_dist is None:
             a.max_dist = 1.0
     except ValueError as e:
@@ -453,13 +464,15 @@ def dist_args(argv: Sequence[str]):
 
 
 def cmd_dist(argv: Sequence[str]) -> int:
-    """mash dist [-d D] [-v P] [-t] [--sparse] [-i] [-l] REF.msh QUERY...: the distance of every QUERY
+    """mash dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] REF.msh QUERY...: the distance of every QUERY
     sketch to every sketch of REF.msh, computed on the GPU; one row per pair on stdout
     (reference, query, distance, p-value, shared/compared hashes), query-major.
       -d  keep pairs with distance <= D (1)     -v  keep pairs with p-value <= P (1)
       -t  table output (ignores -d and -v)      -l  QUERYs list paths
       -i  one query per sequence of a FASTA QUERY
       --sparse  with -d D, D < 1: visit only the pairs that share a hash (the same rows)
+      --top K   per query only its K nearest references (of those within -d D), nearest first;
+                equal common/denom ratios in reference order.  Not with -t or -v P < 1.
     A QUERY ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU with
     REF.msh's k-mer size, seed, sketch size and case rule."""
     a = dist_args(argv)
@@ -504,7 +517,8 @@ def cmd_dist(argv: Sequence[str]) -> int:
         denom = np.concatenate([p[3] for p in parts]) if parts else np.zeros(0, np.int32)
         sys.stdout.write("".join(l + "\n" for l in md.format_table(ref, qry, common, denom)))
         return 0
-    for qi, ri, common, denom in md.dist_blocks(gpu, ref, qry, a.max_dist, block_bytes=1 << 26, sparse=a.sparse):
+    for qi, ri, common, denom in md.dist_blocks(gpu, ref, qry, a.max_dist, block_bytes=1 << 26, sparse=a.sparse,
+                                                top=a.top):
         sys.stdout.write("".join(l + "\n" for l in md.format_lines(ref, qry, qi, ri, common, denom, a.max_dist, a.max_p)))
     return 0
 

@@ -9,7 +9,9 @@ pass a distance threshold.  Host work here: the distance and p-value arithmetic 
 (the one `distance()` below both formats the output and builds the device filter's table, so
 the filter agrees exactly with the printed numbers), blocking, and the text.
 `hymet_mash_dist_sparse` gives the filtered result of a threshold below 1 from the pairs that
-share a hash only (opt-in: sparse_blocks; DESIGN.md §3 Sparse dist).
+share a hash only (opt-in: sparse_blocks; DESIGN.md §3 Sparse dist).  `hymet_mash_dist_topk` and
+`hymet_mash_topk_edges` (csrc/mash_topk.hip) keep the nearest references of every query on the
+device (opt-in: dist_blocks(top=K); DESIGN.md §3 Nearest (top-K)).
 
 The semantics restate Mash's `dist` command from memory of its behaviour.  No Mash binary is
 available to check them against: they are PARITY-UNPINNED, like the .msh schema (msh.py) and
@@ -186,6 +188,50 @@ def select_block(gpu, block, n_rows: int, n_ref: int, table, s: int, cap: int = 
     return row_off.cpu().numpy(), idx[:n].cpu().numpy(), val[:n].cpu().numpy().view(np.uint32)
 
 
+def topk_max() -> int:
+    """The largest `top` (hymet_mash_topk_max)."""
+    from ._lib import load
+    return int(load().hymet_mash_topk_max())
+
+
+def _topk_host(gpu, n_rows: int, top: int, idx, val, cnt):
+    """The device result of a top-K call as host CSR arrays: (row_off int64 [n_rows + 1],
+    reference index int32, packed value uint32), each row nearest first."""
+    gpu.sync()
+    c = cnt.cpu().numpy()
+    written = np.arange(top, dtype=np.int32)[None, :] < c[:, None]
+    row_off = np.r_[0, np.cumsum(c, dtype=np.int64)].astype(np.int64)
+    return (row_off, idx.cpu().numpy().reshape(n_rows, top)[written],
+            val.cpu().numpy().view(np.uint32).reshape(n_rows, top)[written])
+
+
+def topk_block(gpu, block, n_rows: int, n_ref: int, table, s: int, top: int):
+    """hymet_mash_dist_topk over a dense device block: per row the `top` nearest references
+    among those that pass `table` (a device min_common_table; None: among all), nearest first
+    (the order stands at hymet_mash_dist_topk in include/hymet_gpu.h), as host CSR arrays."""
+    from ._lib import ptr
+    torch = gpu.torch
+    idx = gpu.empty(max(1, n_rows * top), torch.int32)
+    val = gpu.empty(max(1, n_rows * top), torch.int32)
+    cnt = gpu.empty(max(1, n_rows), torch.int32)
+    gpu.call("hymet_mash_dist_topk", ptr(block), int(n_rows), int(n_ref), ptr(table) if table is not None else None, int(s),
+             int(top), ptr(idx), ptr(val), ptr(cnt))
+    return _topk_host(gpu, n_rows, top, idx[:n_rows * top], val[:n_rows * top], cnt[:n_rows])
+
+
+def topk_edges(gpu, row_off, n_rows: int, ref_idx, val_in, s: int, top: int):
+    """hymet_mash_topk_edges over a device CSR (as select_block's call or sparse_block leaves it
+    on the device): per row its `top` nearest entries, nearest first, as host CSR arrays."""
+    from ._lib import ptr
+    torch = gpu.torch
+    idx = gpu.empty(max(1, n_rows * top), torch.int32)
+    val = gpu.empty(max(1, n_rows * top), torch.int32)
+    cnt = gpu.empty(max(1, n_rows), torch.int32)
+    gpu.call("hymet_mash_topk_edges", ptr(row_off), int(n_rows), ptr(ref_idx), ptr(val_in), int(s), int(top), ptr(idx),
+             ptr(val), ptr(cnt))
+    return _topk_host(gpu, n_rows, top, idx[:n_rows * top], val[:n_rows * top], cnt[:n_rows])
+
+
 def candidate_min_common(table) -> int:
     """cmin of the sparse path: the fewest shared hashes a pair that passes `table`
     (min_common_table) can have, the smallest t[denom] over denom >= 1.  At least 1 for
@@ -284,14 +330,57 @@ def sparse_blocks(gpu, ref_db: SketchDB, qry_db: SketchDB, max_dist: float, bloc
         yield qi, ri, (v >> 16).astype(np.int32), (v & 0xFFFF).astype(np.int32)
 
 
+def top_blocks(gpu, ref_db: SketchDB, qry_db: SketchDB, top: int, max_dist: float = 1.0, block_bytes: int = 1 << 30,
+               sparse: bool = False) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+    """dist_blocks(top=...): per query at most `top` references, nearest first (the order stands
+    at hymet_mash_dist_topk in include/hymet_gpu.h), among those with distance() <= max_dist.
+    The selection runs on the device over the dense block (the threshold's table fused into it)
+    or, sparse, over the CSR of each range of the sparse path; neither the dense block nor the
+    unselected pairs reach the host.  ValueError for a `top` outside 1..topk_max()."""
+    top = int(top)
+    if not 1 <= top <= topk_max():
+        raise ValueError(f"top {top} outside 1..{topk_max()}")
+    if sparse and not max_dist < 1.0:
+        raise ValueError(f"sparse_blocks: max_dist {max_dist} is not below 1")
+    s = check_compatible(ref_db, qry_db, warn=False)
+    torch = gpu.torch
+    ref, qry = DeviceSketches(gpu, ref_db), DeviceSketches(gpu, qry_db)
+    n_ref = ref.n
+    rows = max(1, int(block_bytes) // (4 * max(n_ref, 1)))
+    table = None
+    if max_dist < 1.0:
+        host_table = min_common_table(s, ref_db.k, max_dist)
+        table = torch.from_numpy(host_table.view(np.int16).copy()).to(gpu.dev)
+    if sparse:
+        cmin, max_pairs = candidate_min_common(host_table), max(0, int(block_bytes) // 16)
+        ranges = sparse_ranges(qry.n, rows, lambda a, b: sparse_block(gpu, ref, qry, a, b, s, table, cmin, max_pairs))
+    else:
+        ranges = (("dense", q0, min(qry.n, q0 + rows), None) for q0 in range(0, qry.n, rows))
+    for path, q0, q1, got in ranges:
+        if n_ref == 0:
+            z = np.zeros(0, np.int32)
+            yield z, z, z, z
+            continue
+        if path == "dense":
+            row_off, ri, v = topk_block(gpu, dist_block(gpu, ref, qry, q0, q1, s), q1 - q0, n_ref, table, s, top)
+        else:
+            row_off, ri, v = topk_edges(gpu, got[0], q1 - q0, got[1], got[2], s, top)
+        qi = np.repeat(np.arange(q0, q1, dtype=np.int32), np.diff(row_off))
+        yield qi, ri, (v >> 16).astype(np.int32), (v & 0xFFFF).astype(np.int32)
+
+
 def dist_blocks(gpu, ref_db: SketchDB, qry_db: SketchDB, max_dist: float = 1.0, block_bytes: int = 1 << 30,
-                sparse: bool = False) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+                sparse: bool = False, top: int = 0) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
     """`mash dist` of two DBs on the device: yields (q_index, r_index, common, denom) int32
     arrays, query-major (for each query in DB order, the references in DB order), one tuple per
     block of queries.  Both DBs are uploaded once; a block holds as many queries as keep the
     dense result within block_bytes, and the concatenated result does not depend on it.
     max_dist >= 1: every pair; below, the pairs with distance() <= max_dist, filtered on the
-    device (min_common_table).  sparse: the same result through sparse_blocks (max_dist < 1)."""
+    device (min_common_table).  sparse: the same result through sparse_blocks (max_dist < 1).
+    top > 0: per query only the `top` nearest of those references, nearest first (top_blocks)."""
+    if top:
+        yield from top_blocks(gpu, ref_db, qry_db, top, max_dist, block_bytes, sparse)
+        return
     if sparse:
         yield from sparse_blocks(gpu, ref_db, qry_db, max_dist, block_bytes)
         return

@@ -331,6 +331,40 @@ int hymet_mash_dist_sparse(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t
  * every index must lie inside d_parent.  Queued on the context's stream. */
 int hymet_mash_link_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_rows, int64_t q_begin,
                           const int32_t *d_ref_idx, int32_t *d_parent, uint64_t *d_n_links);
+/* Nearest references (`dist --top K`): the K best entries of every row of a dist result.
+ * Order: nearest first by the exact rational common / denom, descending, with 0 / 0 counting as 1
+ * (its distance is 0); equal rationals, 1/2 and 500/1000 for example, by reference index,
+ * ascending.  The order is defined on the two integers, not on the double the host's distance()
+ * returns; that distance is non-increasing in common / denom, so a row's distances never decrease.
+ * The device compares rank << 32 | position with rank = 2^31 - floor(common * 2^31 / denom) (0 for
+ * denom == 0): with denom <= 2^14 two different fractions differ by at least 2^-28, so the rank is
+ * strictly smaller for the larger fraction and equal for equal fractions; no float arithmetic.
+ * Row r of the output occupies [r * K, r * K + d_cnt[r]) of d_idx (reference index) and d_val
+ * (packed common << 16 | denom), d_cnt[r] = min(K, the row's competing entries); entries beyond
+ * the count are not written.  An entry with denom > s or common > denom does not compete.
+ * hymet_mash_topk_max(): the largest K.  hymet_mash_topk_tune: the fewest entries a chunk of a row
+ * holds when a row is split over several workgroups (a call with few rows fills the card that
+ * way; the result does not depend on it); 0 restores the default, -1 leaves the setting.
+ * Process-wide, for tests and timing. */
+int32_t hymet_mash_topk_max(void);
+int hymet_mash_topk_tune(int chunk_entries);
+/* Over a dense block (n_rows x n_ref, as hymet_mash_dist writes it).  d_min_common: the s + 1
+ * uint16 entries of hymet_mash_dist_select's filter, only entries with common >=
+ * d_min_common[denom] compete; NULL: every entry competes.  Checked before anything is launched or
+ * written (HYMET_E_ARG): K in 1..hymet_mash_topk_max(), s in 1..hymet_sketch_max_size(), n_rows and
+ * n_ref in [0, 2^31).  Zero rows or zero references is not an error (the counts are 0).  Queued on
+ * the context's stream; does not synchronise. */
+int hymet_mash_dist_topk(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n_ref,
+                         const uint16_t *d_min_common, int32_t s, int32_t K, int32_t *d_idx, uint32_t *d_val,
+                         int32_t *d_cnt);
+/* Over a CSR (d_row_off: n_rows + 1 int64, then reference index and packed value per entry, as
+ * hymet_mash_dist_select and hymet_mash_dist_sparse write it): every entry of a row competes, and
+ * since a row's reference indices ascend the result equals hymet_mash_dist_topk's over the dense
+ * block with the filter that made the CSR.  Rows shorter than 2^31 entries.  Checks as above.
+ * The offsets are read on the device only: queued on the context's stream, does not synchronise. */
+int hymet_mash_topk_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_rows, const int32_t *d_ref_idx,
+                          const uint32_t *d_val_in, int32_t s, int32_t K, int32_t *d_idx, uint32_t *d_val,
+                          int32_t *d_cnt);
 
 /* --------------------------------------------------- minimizer index (minimap2 -d)
  * Replaces `minimap2 -I2g -d reference.mmi combined_genomes.fasta` (scripts/minimap2.sh:12):
