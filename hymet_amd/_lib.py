@@ -55,6 +55,10 @@ _SIGS = {
     "hymet_screen_winner": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "hymet_sketch_max_size": (_i64, []),
     "hymet_sketch_batch": (_i32, [_vp, _vp, _vp, _i64, _i32, _u32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "hymet_sketch_counted": (_i32, [_vp, _vp, _vp, _i64, _i32, _u32, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                    _vp]),
+    "hymet_sketch_counted_max_size": (_i32, []),
+    "hymet_sketch_counted_tune": (_i32, [_i32]),
     "hymet_mash_dist": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "hymet_mash_dist_tile": (_i32, [_i32]),
     "hymet_mash_dist_tune": (_i32, [_i32, _i32]),

@@ -23,14 +23,16 @@
         == scripts/downloadDB.py:178-249 offline (detailed_taxonomy.tsv, combined_genomes.fasta)
     python -m hymet_amd.cli eval-cami [--pred-profile ... --outdir D]
         == tools/eval_cami.py (CAMI profile and contig metrics)
-    python -m hymet_amd.cli sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] -o PREFIX FILE...
+    python -m hymet_amd.cli sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] -o PREFIX FILE...
         == mash sketch (builds the sketch DB the screen reads; the reference downloads its DBs,
-           so there is no stage script and no scripts/ wrapper for it)
-    python -m hymet_amd.cli dist [-d D] [-v P] [-t] [-i] [-l] REF.msh QUERY...
-        == mash dist (all-pairs distances between sketch DBs; QUERY is .msh or FASTA; like
-           sketch, not a stage of the reference workflow)
+           so there is no stage script and no scripts/ wrapper for it).  FILE is FASTA or FASTQ;
+           -r: each FILE is a read set, -m M: keep only k-mers seen at least M times
+    python -m hymet_amd.cli dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] REF.msh QUERY...
+        == mash dist (all-pairs distances between sketch DBs; QUERY is .msh, FASTA or FASTQ,
+           with -r / -m M a read set; like sketch, not a stage of the reference workflow)
     python -m hymet_amd.cli mash-screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE...
-        == mash screen (the rows on stdout, in sketch order; -w: winner-take-all)
+        == mash screen (the rows on stdout, in sketch order; -w: winner-take-all; FILE is FASTA
+           or FASTQ)
     python -m hymet_amd.cli derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [-i] [-l] INPUT...
         single-linkage clusters of the INPUT sketches under a distance threshold, one
         representative per cluster, optionally the reduced .msh (no Mash command does this)
@@ -330,12 +332,23 @@ def cmd_download_db(argv: Sequence[str]) -> int:
 
 
 # ------------------------------------------------------------------ sketch (mash sketch)
-SKETCH_USAGE = "usage: sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] -o PREFIX FILE..."
+SKETCH_USAGE = "usage: sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] -o PREFIX FILE..."
+
+
+def parse_size(text: str) -> int:
+    """A genome size as `mash sketch -g` takes it: a positive number with an optional k / m / g /
+    t suffix in either case (4.6m = 4,600,000)."""
+    mult = {"k": 10 ** 3, "m": 10 ** 6, "g": 10 ** 9, "t": 10 ** 12}.get(text[-1:].lower())
+    v = float(text[:-1] if mult else text) * (mult or 1)
+    if not v >= 1:
+        raise ValueError(f"{text}: not a size")
+    return int(round(v))
 
 
 def sketch_args(argv: Sequence[str]):
     """`mash sketch`'s flag letters.  Returns the parsed namespace, or None after printing the
-    usage line (unknown flag, -n, no -o, no FILE)."""
+    usage line (unknown flag, -n, no -o, no FILE, -m below 1, -r or -m above 1 with -i, a -g that
+    is no size).  a.reads is set by -r and by -m above 1."""
     class _Parser(argparse.ArgumentParser):
         def error(self, message):
             raise ValueError(message)
@@ -348,6 +361,9 @@ def sketch_args(argv: Sequence[str]):
     p.add_argument("-Z", action="store_true", dest="preserve_case")
     p.add_argument("-l", action="store_true", dest="lists")
     p.add_argument("-n", action="store_true", dest="noncanonical")
+    p.add_argument("-r", action="store_true", dest="reads")
+    p.add_argument("-m", type=int, default=1, dest="min_copies")
+    p.add_argument("-g", type=parse_size, default=None, dest="genome_size")
     p.add_argument("-o", dest="out")
     p.add_argument("-h", action="store_true", dest="help")
     p.add_argument("files", nargs="*")
@@ -358,6 +374,11 @@ def sketch_args(argv: Sequence[str]):
             raise ValueError("")
         if a.noncanonical:
             raise ValueError("-n: noncanonical sketches are not supported")
+        if a.min_copies < 1:
+            raise ValueError(f"-m {a.min_copies}: the minimum number of copies is at least 1")
+        a.reads = a.reads or a.min_copies > 1
+        if a.reads and a.individual:
+            raise ValueError("-r / -m does not go with -i: a read set is one sketch per FILE")
         if not a.out:
             raise ValueError("-o PREFIX is required")
         if not a.files:
@@ -380,13 +401,18 @@ def expand_lists(files: Sequence[str]) -> List[str]:
 
 
 def cmd_sketch(argv: Sequence[str]) -> int:
-    """mash sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] -o PREFIX FILE...: sketch each FILE
-    (each record with -i) on the GPU and write PREFIX.msh (the suffix is not doubled).
+    """mash sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] -o PREFIX FILE...:
+    sketch each FILE (each record with -i) on the GPU and write PREFIX.msh (the suffix is not
+    doubled).  A FILE is FASTA or FASTQ (gzip too).
       -k  k-mer size, 1..32 (21)        -s  sketch size (1000)       -S  hash seed (42)
       -i  one reference per sequence    -Z  preserve case            -l  FILEs list paths
-    Known limits: -n (noncanonical), protein alphabets and read options (-r, -m) are not
-    supported, and hash lists are always written 64 bits wide, also for k <= 16 where Mash
-    writes 32-bit lists (this project's reader widens either form)."""
+      -r  each FILE is a read set: one sketch per FILE, its length the estimated genome size;
+          one stderr line per FILE with that estimate and the estimated coverage
+      -m  with -r: keep only k-mers seen at least M times in the FILE (1); M > 1 implies -r
+      -g  with -r: the genome size to record instead of the estimate (k / m / g suffix allowed)
+    Known limits: -n (noncanonical), protein alphabets and the Bloom filter (-b) are not
+    supported, -r does not go with -i, and hash lists are always written 64 bits wide, also for
+    k <= 16 where Mash writes 32-bit lists (this project's reader widens either form)."""
     a = sketch_args(argv)
     if a is None:
         return 2
@@ -397,7 +423,15 @@ def cmd_sketch(argv: Sequence[str]) -> int:
     out = a.out if a.out.endswith(".msh") else a.out + ".msh"
     gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
     print("Sketching...", file=sys.stderr)
-    db = sk.sketch_files(gpu, files, k=a.k, seed=a.seed, s=a.s, individual=a.individual, preserve_case=a.preserve_case)
+    info = []
+    try:
+        db = sk.sketch_files(gpu, files, k=a.k, seed=a.seed, s=a.s, individual=a.individual, preserve_case=a.preserve_case,
+                             reads=a.reads, min_copies=a.min_copies, genome_size=a.genome_size, read_info=info)
+    except ValueError as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        return 1
+    for name, size, cov in info:
+        print(f"{name}: estimated genome size {size:g}, estimated coverage {cov:.3g}", file=sys.stderr)
     if db.n_refs == 0:
         print("ERROR: no sequences to sketch.", file=sys.stderr)
         return 1
@@ -407,17 +441,20 @@ def cmd_sketch(argv: Sequence[str]) -> int:
 
 
 # ------------------------------------------------------------------ dist (mash dist)
-DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] REF.msh QUERY..."
+DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] REF.msh QUERY..."
 
 
 def dist_args(argv: Sequence[str]):
     """`mash dist`'s flag letters.  Returns the parsed namespace, or None after printing the
-    usage line (unknown flag, no REF.msh, no QUERY)."""
+    usage line (unknown flag, no REF.msh, no QUERY, -m below 1, -r or -m above 1 with -i or with
+    nothing but .msh QUERYs).  a.reads is set by -r and by -m above 1."""
     class _Parser(argparse.ArgumentParser):
         def error(self, message):
             raise ValueError(message)
 
     p = _Parser(prog="dist", add_help=False, allow_abbrev=False)
+    p.add_argument("-r", action="store_true", dest="reads")
+    p.add_argument("-m", type=int, default=1, dest="min_copies")
     p.add_argument("-d", type=float, default=None, dest="max_dist")
     p.add_argument("-v", type=float, default=1.0, dest="max_p")
     p.add_argument("-t", action="store_true", dest="table")
@@ -436,6 +473,13 @@ def dist_args(argv: Sequence[str]):
             raise ValueError("no REF.msh")
         if len(a.files) < 2:
             raise ValueError("no QUERY")
+        if a.min_copies < 1:
+            raise ValueError(f"-m {a.min_copies}: the minimum number of copies is at least 1")
+        a.reads = a.reads or a.min_copies > 1
+        if a.reads and a.individual:
+            raise ValueError("-r / -m does not go with -i: a read set is one sketch per QUERY")
+        if a.reads and not a.lists and all(q.endswith(".msh") for q in a.files[1:]):
+            raise ValueError("-r / -m apply to sequence QUERYs: every QUERY is a .msh")
         if a.sparse and a.table:
             raise ValueError("--sparse does not go with -t: the table holds every pair")
         if a.sparse and a.max_dist is None:
@@ -464,7 +508,7 @@ def dist_args(argv: Sequence[str]):
 
 
 def cmd_dist(argv: Sequence[str]) -> int:
-    """mash dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] REF.msh QUERY...: the distance of every QUERY
+    """mash dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] REF.msh QUERY...: the distance of every QUERY
     sketch to every sketch of REF.msh, computed on the GPU; one row per pair on stdout
     (reference, query, distance, p-value, shared/compared hashes), query-major.
       -d  keep pairs with distance <= D (1)     -v  keep pairs with p-value <= P (1)
@@ -473,8 +517,10 @@ def cmd_dist(argv: Sequence[str]) -> int:
       --sparse  with -d D, D < 1: visit only the pairs that share a hash (the same rows)
       --top K   per query only its K nearest references (of those within -d D), nearest first;
                 equal common/denom ratios in reference order.  Not with -t or -v P < 1.
-    A QUERY ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU with
-    REF.msh's k-mer size, seed, sketch size and case rule."""
+      -r  each sequence QUERY is a read set (one sketch per QUERY)
+      -m  with -r: keep only k-mers seen at least M times in the QUERY (1); M > 1 implies -r
+    A QUERY ending in .msh is loaded; any other is FASTA or FASTQ (gzip too), sketched on the GPU
+    with REF.msh's k-mer size, seed, sketch size and case rule.  -r / -m need such a QUERY."""
     a = dist_args(argv)
     if a is None:
         return 2
@@ -488,13 +534,17 @@ def cmd_dist(argv: Sequence[str]) -> int:
         print("dist: no QUERY", file=sys.stderr)
         print(DIST_USAGE, file=sys.stderr)
         return 2
+    if a.reads and all(q.endswith(".msh") for q in queries):
+        print("dist: -r / -m apply to sequence QUERYs: every QUERY is a .msh", file=sys.stderr)
+        print(DIST_USAGE, file=sys.stderr)
+        return 2
     gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
     dbs, fasta = [], []
 
     def flush():      # consecutive FASTA queries are sketched in one call
         if fasta:
             dbs.append(sk.sketch_files(gpu, fasta, k=ref.k, seed=ref.seed, s=ref.sketch_size, individual=a.individual,
-                                       preserve_case=ref.preserve_case))
+                                       preserve_case=ref.preserve_case, reads=a.reads, min_copies=a.min_copies))
             fasta.clear()
 
     try:
@@ -638,7 +688,7 @@ def cmd_derep(argv: Sequence[str]) -> int:
       --sparse  visit only the pairs that share a hash (the same clusters)
       -k -s -S  k-mer size, sketch size and seed for FASTA INPUTs when no INPUT is a .msh
                 (21, 1000, 42); otherwise the first .msh INPUT's parameters are used
-    An INPUT ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU."""
+    An INPUT ending in .msh is loaded; any other is FASTA or FASTQ (gzip too), sketched on the GPU."""
     a = derep_args(argv)
     if a is None:
         return 2
@@ -675,7 +725,7 @@ def cmd_triangle(argv: Sequence[str]) -> int:
     computed on the GPU: a first line with the number of sketches, then per sketch its name and
     the distance to every earlier one.
       -i  one sketch per sequence of a FASTA INPUT      -l  INPUTs list paths
-    An INPUT ending in .msh is loaded; any other is FASTA (gzip too), sketched on the GPU with
+    An INPUT ending in .msh is loaded; any other is FASTA or FASTQ (gzip too), sketched on the GPU with
     the first .msh INPUT's parameters, or k = 21, s = 1000, seed 42 when there is none."""
     a = triangle_args(argv)
     if a is None:
@@ -735,7 +785,7 @@ def mash_screen_args(argv: Sequence[str]):
 
 def cmd_mash_screen(argv: Sequence[str]) -> int:
     """mash screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE...: how well each sketch of
-    DB.msh is contained in the pooled FILEs (FASTA, gzip too), computed on the GPU; one row per
+    DB.msh is contained in the pooled FILEs (FASTA or FASTQ, gzip too), computed on the GPU; one row per
     reference on stdout in sketch order (identity, shared-hashes, median-multiplicity, p-value,
     name, comment).
       -w  winner-take-all: each hash found in the pool is credited to the best-scoring
@@ -748,10 +798,10 @@ def cmd_mash_screen(argv: Sequence[str]) -> int:
     from . import screen as scr
     from ._lib import Gpu
     from .msh import load_db
-    from .seqio import DevicePool, read_fasta
+    from .seqio import DevicePool, read_seqs
     db = load_db(a.db)
     gpu = Gpu(int(os.environ.get("HYMET_DEVICE", "0")))
-    ss = read_fasta(list(a.inputs))
+    ss = read_seqs(list(a.inputs))
     res = scr.screen(gpu, DevicePool(gpu, ss, DevicePool.ALPHA_MASH), [db], winner=a.winner)[0]
     sys.stdout.write("".join(l + "\n" for l in res.lines(v_max=a.max_p, identity_min=a.min_identity)))
     return 0

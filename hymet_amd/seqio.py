@@ -1,4 +1,4 @@
-"""FASTA input and the packed on-device sequence pool.
+"""FASTA / FASTQ input and the packed on-device sequence pool.
 
 A *pool* is every sequence of a set of FASTA files concatenated with one 'N' separator
 between records, so that no k-mer or minimizer window can span two records (the invalid
@@ -6,6 +6,8 @@ separator resets every rolling state).  On the device it is held packed: 2-bit c
 (16 bases / uint32) + an invalid-base bitmask (32 bases / uint32) -- 0.375 B per base.
 The reference reads FASTA through Mash's and minimap2's kseq readers: a record name is the
 first whitespace-delimited token after '>', the rest of the header line is the comment.
+Sequencing reads come as FASTQ: read_seqs takes either format per file (parse_fastq_bytes, kseq's
+FASTQ rules); read_fasta stays FASTA-only for the stage drop-ins and the mapper.
 """
 from __future__ import annotations
 
@@ -93,6 +95,102 @@ def read_fasta(paths) -> SeqSet:
     for fi, p in enumerate(paths):
         with _open(p) as f:
             r = parse_fasta_bytes(f.read())
+        recs.extend(r)
+        file_of.extend([fi] * len(r))
+    return from_records(recs, [str(p) for p in paths], file_of)
+
+
+def _fastq_head(head: bytes):
+    parts = head[1:].split(None, 1)
+    return (parts[0].decode() if parts else "", parts[1].decode() if len(parts) > 1 else "")
+
+
+def _fastq_four_lines(data: bytes):
+    """The records of a FASTQ text in which every record is exactly four lines (header, sequence,
+    '+' line, quality of the sequence's length), or None when the text is not of that shape.
+    data: no '\\r', ends with a line break.  The shape is checked on the line-start bytes and
+    line lengths as arrays, and the fields are cut with whole-text operations: nothing here
+    loops over the records."""
+    import re
+    a = np.frombuffer(data, dtype=np.uint8)
+    nl = np.flatnonzero(a == 10)
+    n_lines = len(nl)
+    if n_lines == 0 or n_lines % 4:
+        return None
+    starts = np.empty(n_lines, np.int64)
+    starts[0] = 0
+    starts[1:] = nl[:-1] + 1
+    lens = nl - starts
+    # a sequence line that itself starts with '+' would end the sequence under the general rules
+    if not ((a[starts[0::4]] == 64).all() and (a[starts[2::4]] == 43).all() and (a[starts[1::4]] != 43).all()
+            and (lens[1::4] == lens[3::4]).all()):
+        return None
+    lines = data.split(b"\n")                      # n_lines entries and a last empty one
+    heads = b"\n".join(lines[0:n_lines:4])
+    names = b"\n".join(re.findall(rb"^@[^\S\n]*(\S*)", heads, re.M)).decode().split("\n")
+    comments = b"\n".join(re.findall(rb"^@[^\S\n]*\S*[^\S\n]*(.*)$", heads, re.M)).decode().split("\n")
+    return list(zip(names, comments, lines[1:n_lines:4]))
+
+
+def parse_fastq_bytes(data: bytes):
+    """[(name, comment, sequence)] of a FASTQ text, by kseq's rules: a record starts at a line
+    beginning with '@' (name = the first whitespace-delimited token of that line, comment = the
+    rest); its sequence is the following lines up to a line beginning with '+'; its quality is
+    the lines after that until their summed length reaches the sequence's length -- so a quality
+    line that starts with '@' or '>' is not a record start.  '\\r' is stripped, a missing final
+    line break is fine, lines before the first record are skipped.  ValueError, naming the
+    record, when the quality is shorter than the sequence at the end of the text (a truncated
+    file) or longer than it.  Texts whose records are all four lines take a path without a
+    loop over the records (_fastq_four_lines)."""
+    data = bytes(data).replace(b"\r", b"")
+    if not data.strip():
+        return []
+    if not data.endswith(b"\n"):
+        data += b"\n"
+    out = _fastq_four_lines(data)
+    if out is not None:
+        return out
+    out = []
+    lines = data.split(b"\n")
+    lines.pop()                                    # the empty piece behind the last line break
+    i, n = 0, len(lines)
+    while i < n:
+        if not lines[i].startswith(b"@"):
+            i += 1
+            continue
+        name, comment = _fastq_head(lines[i])
+        i += 1
+        seq = []
+        while i < n and not lines[i].startswith(b"+"):
+            seq.append(lines[i])
+            i += 1
+        seq = b"".join(seq)
+        i += 1                                     # the '+' line
+        q = 0
+        while i < n and q < len(seq):
+            q += len(lines[i])
+            i += 1
+        if q != len(seq):
+            raise ValueError(f"FASTQ record {name!r}: quality of {q} characters for a sequence of {len(seq)}"
+                             + (" (truncated file?)" if q < len(seq) else ""))
+        out.append((name, comment, seq))
+    return out
+
+
+def read_seqs(paths) -> SeqSet:
+    """read_fasta for FASTA and FASTQ files alike (gzip too): per file, the first byte after
+    leading white space decides -- '@' is FASTQ (parse_fastq_bytes), anything else goes to
+    parse_fasta_bytes.  files / file_of as read_fasta."""
+    import re
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        paths = [paths]
+    recs, file_of = [], []
+    for fi, p in enumerate(paths):
+        with _open(p) as f:
+            data = f.read()
+        m = re.search(rb"\S", data)
+        fastq = m is not None and data[m.start():m.start() + 1] == b"@"
+        r = parse_fastq_bytes(data) if fastq else parse_fasta_bytes(data)
         recs.extend(r)
         file_of.extend([fi] * len(r))
     return from_records(recs, [str(p) for p in paths], file_of)

@@ -121,7 +121,70 @@ def sketch_pool(gpu, pool, group_of=None, k: int = 21, seed: int = 42, s: int = 
     return [rows[r, :c] for r, c in enumerate(cnt.tolist())]    # views of the one host copy
 
 
+def max_counted_sketch_size() -> int:
+    return int(load().hymet_sketch_counted_max_size())
+
+
+def sketch_pool_counted(gpu, pool, group_of, k: int, seed: int, s: int, min_copies: int,
+                        chunk_bases: Optional[int] = None) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """Mash `sketch -r -m M` of a packed pool: per group of records the s smallest canonical
+    k-mer hashes seen at least min_copies times over the whole group, sorted (np.uint64), and
+    each one's multiplicity (np.uint32) -- one (hashes, counts) pair per group id in
+    0..max(group_of); group_of=None: one sketch per record.  Exact, whatever the chunking
+    (csrc/sketch_counted.hip).  One call of hymet_sketch_counted and one copy to the host.
+    sketch_pool_counted.stats holds what the last call did: {"passes", "merged"} (passes over the
+    pool; (hash, count) pairs that went through a per-sketch merge)."""
+    torch = gpu.torch
+    ss = pool.ss
+    if group_of is None:
+        group_of = np.arange(ss.n, dtype=np.int64)
+    group_of = np.asarray(group_of, np.int64)
+    if len(group_of) != ss.n:
+        raise ValueError("sketch_pool_counted: group_of needs one entry per record")
+    n_sk = int(group_of.max()) + 1 if len(group_of) else 0
+    sketch_pool_counted.stats = {"passes": 0, "merged": 0}
+    if n_sk == 0:
+        return []
+    s = int(s)
+    cs, cb, ce = plan_chunks(ss.starts, ss.lengths, group_of, k, int(chunk_bases or DEFAULT_CHUNK_BASES))
+    # one buffer, one copy: the rows (8 B), their multiplicities (4 B), the rows' lengths (4 B)
+    w_cnt = (n_sk * s + 1) // 2
+    out = gpu.empty(n_sk * s + w_cnt + (n_sk + 1) // 2, torch.int64)
+    d_cnt = ctypes.c_void_p(out.data_ptr() + 8 * n_sk * s)
+    d_n = ctypes.c_void_p(out.data_ptr() + 8 * (n_sk * s + w_cnt))
+    stats = (ctypes.c_int64 * 2)()
+    gpu.call("hymet_sketch_counted", ptr(pool.w2b), ptr(pool.wmask), pool.n_bases, int(k), int(seed), s, int(min_copies),
+             len(cs), cs.ctypes.data_as(ctypes.c_void_p), cb.ctypes.data_as(ctypes.c_void_p),
+             ce.ctypes.data_as(ctypes.c_void_p), n_sk, ptr(out), d_cnt, d_n, ctypes.cast(stats, ctypes.c_void_p))
+    sketch_pool_counted.stats = {"passes": int(stats[0]), "merged": int(stats[1])}
+    host = out.cpu().numpy()
+    rows = host[:n_sk * s].view(np.uint64).reshape(n_sk, s)
+    cnts = host[n_sk * s:n_sk * s + w_cnt].view(np.uint32)[:n_sk * s].reshape(n_sk, s)
+    n = host[n_sk * s + w_cnt:].view(np.int32)[:n_sk]
+    return [(rows[r, :c], cnts[r, :c]) for r, c in enumerate(n.tolist())]    # views of the one host copy
+
+
+sketch_pool_counted.stats = {"passes": 0, "merged": 0}
+
+
 # ------------------------------------------------------------------ metadata (unpinned)
+def read_set_length(hashes, s: int, k: int, genome_size: Optional[int] = None) -> int:
+    """The `length` a read-set sketch carries in the .msh -- this project's rule, restating
+    Mash's genome-size estimate from memory and unpinned like the other metadata: genome_size
+    when given (`-g`); else for a full row (n = s hashes) the estimate n * 2^b / max(h_max, 1)
+    rounded to the nearest integer (halves up), with b = 64, or 32 for k <= 16, and h_max the
+    row's largest hash -- the hash space divided by the mean gap of the kept hashes; else (the
+    row is not full: every qualifying k-mer is in it) n."""
+    if genome_size is not None:
+        return int(genome_size)
+    n = len(hashes)
+    if n < int(s) or n == 0:
+        return n
+    d = max(int(hashes[-1]), 1)
+    return (2 * n * (1 << (32 if int(k) <= 16 else 64)) + d) // (2 * d)
+
+
+
 def _join(name: str, comment: str) -> str:
     return f"{name} {comment}" if comment else name
 
@@ -147,21 +210,37 @@ def _warn(msg: str):
 
 def sketch_files(gpu, paths: Sequence[str], k: int = 21, seed: int = 42, s: int = 1000, individual: bool = False,
                  preserve_case: bool = False, batch_bases: int = DEFAULT_BATCH_BASES,
-                 chunk_bases: Optional[int] = None) -> SketchDB:
-    """`mash sketch [-i] [-Z] -k K -s S -S SEED FILE...` -> SketchDB, references in argument
-    order.  The files are read (gzip too, seqio) and sketched in batches of about batch_bases
-    bases -- read, pack (DevicePool), sketch_pool -- so neither the host nor HBM ever holds the
-    whole collection; one file is the smallest unit of a batch.
+                 chunk_bases: Optional[int] = None, reads: bool = False, min_copies: int = 1,
+                 genome_size: Optional[int] = None, read_info: Optional[list] = None) -> SketchDB:
+    """`mash sketch [-i] [-Z] [-r] [-m M] [-g SIZE] -k K -s S -S SEED FILE...` -> SketchDB,
+    references in argument order.  The files are FASTA or FASTQ (gzip too, seqio.read_seqs) and
+    are sketched in batches of about batch_bases bases -- read, pack (DevicePool), sketch_pool --
+    so neither the host nor HBM ever holds the whole collection; one file is the smallest unit of
+    a batch.
 
     File mode: one reference per file (file_meta); a file with no record of k bases is skipped
     with a warning.  individual (`-i`): one reference per record, named and commented as the
     record; shorter records are skipped with a warning.  preserve_case (`-Z`): lower-case bases
-    are not k-mer letters.  Metadata rules unpinned (module docstring)."""
-    from .seqio import DevicePool, from_records, read_fasta
+    are not k-mer letters.  Metadata rules unpinned (module docstring).
+
+    reads (`-r`; min_copies > 1 implies it): every file is a read set and one sketch, named and
+    commented by file_meta as in file mode, holding the s smallest hashes seen at least
+    min_copies (`-m`) times in the file (sketch_pool_counted).  Its length is this project's
+    rule (read_set_length): genome_size (`-g`) if given, else the genome-size estimate of a full
+    row, else the number of hashes.  The multiplicities are not written to the .msh; read_info,
+    when a list, receives per sketch (name, length, mean multiplicity of the kept hashes -- the
+    estimated coverage).  Not with individual (ValueError)."""
+    from .seqio import DevicePool, from_records, read_seqs
     if not 1 <= int(k) <= 32:
         raise ValueError(f"k={k}: Mash k-mer sizes are 1..32")
-    if not 1 <= int(s) <= max_sketch_size():
-        raise ValueError(f"sketch size {s}: supported sizes are 1..{max_sketch_size()}")
+    if int(min_copies) < 1:
+        raise ValueError(f"min_copies={min_copies}: at least 1")
+    reads = bool(reads) or int(min_copies) > 1
+    if reads and individual:
+        raise ValueError("a read set is one sketch per file: reads does not go with individual")
+    s_max = max_counted_sketch_size() if reads else max_sketch_size()
+    if not 1 <= int(s) <= s_max:
+        raise ValueError(f"sketch size {s}: supported sizes are 1..{s_max}" + (" for read sets" if reads else ""))
     alpha = DevicePool.ALPHA_MASH_PRESERVE_CASE if preserve_case else DevicePool.ALPHA_MASH
     max_refs = max(1, _MAX_OUT_BYTES // (8 * int(s)))
     names: List[str] = []
@@ -175,7 +254,17 @@ def sketch_files(gpu, paths: Sequence[str], k: int = 21, seed: int = 42, s: int 
         nonlocal recs, group_of, meta, bases
         if meta:
             pool = DevicePool(gpu, from_records(recs), alpha)
-            rows = sketch_pool(gpu, pool, np.asarray(group_of, np.int64), k, seed, s, chunk_bases)
+            if reads:
+                pairs = sketch_pool_counted(gpu, pool, np.asarray(group_of, np.int64), k, seed, s, int(min_copies),
+                                            chunk_bases)
+                rows = [h for h, _ in pairs]
+                meta = [(nm, cm, min(read_set_length(h, s, k, genome_size), (1 << 63) - 1))   # SketchDB lengths: int64
+                        for (nm, cm, _), h in zip(meta, rows)]
+                if read_info is not None:
+                    read_info.extend((nm, ln, float(c.mean()) if len(c) else 0.0)
+                                     for (nm, _, ln), (_, c) in zip(meta, pairs))
+            else:
+                rows = sketch_pool(gpu, pool, np.asarray(group_of, np.int64), k, seed, s, chunk_bases)
             del pool
             for (nm, cm, ln), h in zip(meta, rows):
                 names.append(nm)
@@ -185,7 +274,7 @@ def sketch_files(gpu, paths: Sequence[str], k: int = 21, seed: int = 42, s: int 
         recs, group_of, meta, bases = [], [], [], 0
 
     for p in paths:
-        ss = read_fasta([p])
+        ss = read_seqs([p])
         if individual:
             for i in range(ss.n):
                 L = int(ss.lengths[i])

@@ -236,6 +236,29 @@ int hymet_sketch_batch(hymet_ctx *ctx, const uint32_t *d_2b, const uint32_t *d_m
                        int k, uint32_t seed, int32_t s, int64_t n_chunks, const int32_t *h_chunk_sketch,
                        const int64_t *h_chunk_begin, const int64_t *h_chunk_end, int32_t n_sketches,
                        uint64_t *d_out, int32_t *d_out_n);
+/* Read-set sketch (`mash sketch -r -m M`): for each sketch the s smallest hashes among those
+ * whose multiplicity over ALL of the sketch's k-mers is >= min_copies, ascending, in d_out
+ * (n_sketches x s uint64), each one's multiplicity in d_out_count (n_sketches x s uint32,
+ * saturating) and the number of entries in d_out_n.  Exact: no hash threshold is supplied or
+ * guessed; the result does not depend on the chunking, the schedule or the tuning.  Pool,
+ * hashing and the chunk plan are hymet_sketch_batch's, with the same plan checks before any
+ * launch; in addition s must be in 1..hymet_sketch_counted_max_size(), min_copies >= 1, and a
+ * sketch whose chunks span 2^32 positions or more is refused (the counts are 32 bits).  With
+ * min_copies = 1 the rows equal hymet_sketch_batch's.  The pool is hashed in one or more passes
+ * (a sketch whose row is still short after a pass is hashed again above the largest hash dealt
+ * with); the call returns when every sketch is done, the stream idle.  h_stats (nullable, host):
+ * [0] passes, [1] (hash, count) pairs that went through a per-sketch merge. */
+int hymet_sketch_counted(hymet_ctx *ctx, const uint32_t *d_2b, const uint32_t *d_mask, int64_t n_bases,
+                         int k, uint32_t seed, int32_t s, int32_t min_copies, int64_t n_chunks,
+                         const int32_t *h_chunk_sketch, const int64_t *h_chunk_begin,
+                         const int64_t *h_chunk_end, int32_t n_sketches, uint64_t *d_out,
+                         uint32_t *d_out_count, int32_t *d_out_n, int64_t *h_stats);
+/* The largest s of hymet_sketch_counted: 12-byte (hash, count) slots in the CU's 160 KiB. */
+int hymet_sketch_counted_max_size(void);
+/* (hash, count) slots a chunk keeps per pass: 0 = the default (at least s), else 1..
+ * hymet_sketch_counted_max_size().  It changes the number of passes, never the result.  Process-
+ * wide; for tests and timing only, like hymet_mash_topk_tune. */
+int hymet_sketch_counted_tune(int keep);
 
 /* ------------------------------------------------------------ Mash dist (sketch vs sketch)
  * Replaces `mash dist REF.msh QUERY.msh`: for every (reference, query) pair of two sketch DBs
