@@ -69,6 +69,8 @@ _SIGS = {
     "hymet_mash_dist_sparse": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _i32,
                                       _i64, _vp, _vp, _vp, _i64, _c.POINTER(_i64), _vp]),
     "hymet_mash_link_edges": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "hymet_mash_greedy": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _c.POINTER(_i32)]),
+    "hymet_mash_greedy_edges": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _c.POINTER(_i32)]),
     "hymet_mash_topk_max": (_i32, []),
     "hymet_mash_topk_tune": (_i32, [_i32]),
     "hymet_mash_dist_topk": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp]),

@@ -33,9 +33,11 @@
     python -m hymet_amd.cli mash-screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE...
         == mash screen (the rows on stdout, in sketch order; -w: winner-take-all; FILE is FASTA
            or FASTQ)
-    python -m hymet_amd.cli derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [-i] [-l] INPUT...
+    python -m hymet_amd.cli derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [--greedy] [--sparse] [-i]
+                                  [-l] INPUT...
         single-linkage clusters of the INPUT sketches under a distance threshold, one
-        representative per cluster, optionally the reduced .msh (no Mash command does this)
+        representative per cluster, optionally the reduced .msh (no Mash command does this);
+        --greedy: greedy representatives instead, every member within the threshold of its own
     python -m hymet_amd.cli triangle [-i] [-l] INPUT...
         == mash triangle (the lower-triangular distance matrix of the INPUT sketches)
 
@@ -574,7 +576,8 @@ def cmd_dist(argv: Sequence[str]) -> int:
 
 
 # ------------------------------------------------------------------ derep / triangle
-DEREP_USAGE = "usage: derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [--sparse] [-i] [-l] INPUT..."
+DEREP_USAGE = ("usage: derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [--greedy] [--sparse] [-i] [-l] "
+               "INPUT...")
 TRIANGLE_USAGE = "usage: triangle [-i] [-l] INPUT..."
 
 
@@ -593,6 +596,7 @@ def derep_args(argv: Sequence[str]):
     p.add_argument("-s", type=int, default=1000, dest="s")
     p.add_argument("-S", type=int, default=42, dest="seed")
     p.add_argument("--sparse", action="store_true", dest="sparse")
+    p.add_argument("--greedy", action="store_true", dest="greedy")
     p.add_argument("-i", action="store_true", dest="individual")
     p.add_argument("-l", action="store_true", dest="lists")
     p.add_argument("-h", action="store_true", dest="help")
@@ -677,7 +681,7 @@ def _load_inputs(gpu, inputs: Sequence[str], a):
 
 
 def cmd_derep(argv: Sequence[str]) -> int:
-    """derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [--sparse] [-i] [-l] INPUT...:
+    """derep [-d D] [-r longest|first] [-o PREFIX] [-k K] [-s S] [-S SEED] [--greedy] [--sparse] [-i] [-l] INPUT...:
     single-linkage clusters of all INPUT sketches under the Mash distance D, computed on the GPU
     (each pair once, the clusters formed in device memory); one row per sketch on stdout in input
     order (member, representative, cluster index, cluster size) and a summary line on stderr.
@@ -686,6 +690,10 @@ def cmd_derep(argv: Sequence[str]) -> int:
       -o  write PREFIX.msh holding the representatives only (the suffix is not doubled)
       -i  one sketch per sequence of a FASTA INPUT      -l  INPUTs list paths
       --sparse  visit only the pairs that share a hash (the same clusters)
+      --greedy  greedy representatives instead of single linkage: the sketches are taken in the
+                order of -r (longest genome first, or input order), one is kept as a representative
+                unless an earlier representative lies within D of it, and then joins the nearest
+                such; every member lies within D of its representative, no two representatives do
       -k -s -S  k-mer size, sketch size and seed for FASTA INPUTs when no INPUT is a .msh
                 (21, 1000, 42); otherwise the first .msh INPUT's parameters are used
     An INPUT ending in .msh is loaded; any other is FASTA or FASTQ (gzip too), sketched on the GPU."""
@@ -709,10 +717,15 @@ def cmd_derep(argv: Sequence[str]) -> int:
     if db.n_refs == 0:
         print("ERROR: no sequences to sketch.", file=sys.stderr)
         return 1
-    res = dr.cluster(gpu, db, a.max_dist, sparse=a.sparse)
-    reps = dr.representatives(res.labels, db.lengths, a.rule)
-    sys.stdout.write("".join(l + "\n" for l in dr.format_rows(db, res.labels, reps)))
-    print(f"derep: {db.n_refs} sketches, {res.n_links} links, {len(reps)} clusters", file=sys.stderr)
+    if a.greedy:
+        res = dr.cluster_greedy(gpu, db, a.max_dist, rule=a.rule, sparse=a.sparse)
+        labels, reps = dr.greedy_labels(res.rep), dr.greedy_representatives(res.rep)
+    else:
+        res = dr.cluster(gpu, db, a.max_dist, sparse=a.sparse)
+        labels, reps = res.labels, dr.representatives(res.labels, db.lengths, a.rule)
+    sys.stdout.write("".join(l + "\n" for l in dr.format_rows(db, labels, reps)))
+    print(f"derep: {db.n_refs} sketches, {res.n_links} links, {len(reps)} clusters" + (" (greedy)" if a.greedy else ""),
+          file=sys.stderr)
     if a.out:
         out = a.out if a.out.endswith(".msh") else a.out + ".msh"
         print(f"Writing to {out}...", file=sys.stderr)

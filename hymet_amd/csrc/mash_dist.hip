@@ -38,6 +38,10 @@
 //                pairs that share a hash only (hymet_mash_dist_sparse): postings sorted by hash,
 //                one key per shared hash of a pair, keys sorted, runs of cmin or more keys go to
 //                the pair routine.  link_edges: the union-find over that CSR.
+//   greedy / greedy_edges: one round of the greedy choice of representatives over the r < q
+//                entries of a dense block or of that CSR (hymet_mash_greedy, hymet_mash_greedy_edges;
+//                the rules stand at greedy_entry).
+#include "mash_rank.hpp"
 #include "mm_common.hpp"
 #include "sort.hpp"
 
@@ -392,6 +396,187 @@ __global__ __launch_bounds__(kThreads) void link_edges_kernel(const int64_t *__r
     }
 }
 
+// ---- greedy representatives (hymet_mash_greedy, hymet_mash_greedy_edges; DESIGN.md §3 "Greedy derep")
+// The sketches are numbered in priority order.  Walking them in that order, a sketch is a
+// representative iff no earlier representative passes with it, else a member of the nearest of
+// those (mash_rank.hpp's key with the representative's index as the position: equal rationals go
+// to the earlier one).  That is the lexicographically first maximal independent set, reached here
+// as a fixed point over rounds, one launch each.  rep[x] is the state word of sketch x:
+//   kGrOpen     undecided
+//   kGrPending  a member whose representative is not chosen yet: a representative passes with it,
+//               and another passing neighbour is still undecided.  For every other row a
+//               non-representative for good.
+//   x           a representative            r != x, r >= 0   a member of representative r
+// A round scans the passing entries r < q of every row q that is open or pending and reads
+// rep[r] once per entry: the row sees a representative (rep[r] == r), an open neighbour, or a
+// non-representative.  Seeing an open neighbour it waits (pending once it has also seen a
+// representative); seeing none, it is final: its own index without a representative among its
+// neighbours, else the nearest of them, all of which it has seen.
+// Every access to rep inside a launch is a whole-word relaxed agent-scope atomic, as uf_ld's, and
+// as there no fence protocol is needed, because nothing rests on a load being fresh: a word only
+// moves open -> pending -> member or open -> final, "is a representative" and "is not one" are
+// both final once seen, and the one stale value there is, open (or pending, which decides like a
+// member), only makes the reader wait for the next launch, whose boundary makes every store
+// visible.  Nothing spins.  rep[q] is written by the workgroup (wave) that owns row q only.
+// The lowest open row of a range has no open neighbour, so every round decides one row at least,
+// and the round after the last open row is gone settles the pending ones: at most n_rows + 1.
+constexpr int32_t kGrOpen = -1, kGrPending = -2;
+constexpr uint32_t kGrSawRep = 1, kGrSawOpen = 2;
+
+__device__ __forceinline__ uint64_t gr_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+// one passing entry (r, v) of an open or pending row; r lies in [0, q)
+__device__ __forceinline__ void greedy_entry(int32_t *__restrict__ rep, int32_t r, uint32_t v, int64_t q_begin,
+                                             uint64_t &best, uint32_t &flags, int32_t *__restrict__ err) {
+    const int32_t sr = uf_ld(rep + r);
+    if (sr == r) {
+        const uint32_t d = v & 0xffffu;
+        flags |= kGrSawRep;
+        best = gr_min(best, hymet::mash_rank_key(min(v >> 16, d), d, (uint32_t)r));  // common > denom ranks as 1
+    } else if (sr == kGrOpen) {
+        flags |= kGrSawOpen;
+        // a row before this call's range that no earlier call decided: the caller's error
+        if (r < q_begin) __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the state of row q after a round that saw `flags` and the nearest representative `best`
+__device__ __forceinline__ int32_t greedy_decide(int32_t q, uint64_t best, uint32_t flags) {
+    if (flags & kGrSawOpen) return flags & kGrSawRep ? kGrPending : kGrOpen;
+    return flags & kGrSawRep ? (int32_t)(uint32_t)best : q;
+}
+
+// One round over a dense block, in link_kernel's shape: workgroup w takes the rows w, w +
+// gridDim.x, ...; a decided row leaves at once.  count != 0 (a call's first round): every row
+// is scanned and its passing entries are counted into *n_links.  *left: the rows still open or
+// pending after the round.
+__global__ __launch_bounds__(kThreads) void greedy_kernel(const uint32_t *__restrict__ blk, int64_t n_rows, int64_t n,
+                                                          int64_t q_begin, const uint16_t *__restrict__ minc, int s,
+                                                          int count, int32_t *__restrict__ rep,
+                                                          unsigned long long *__restrict__ n_links,
+                                                          int32_t *__restrict__ left, int32_t *__restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ unsigned long long ws[kWaves], ws_best[kWaves];
+    __shared__ uint32_t ws_flags[kWaves];
+    __shared__ int32_t s_state;
+    uint16_t *tab = reinterpret_cast<uint16_t *>(smem);
+    for (int e = threadIdx.x; e <= s; e += kThreads) tab[e] = minc[e];
+    unsigned long long c = 0;
+    int32_t n_left = 0;  // thread 0's
+    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        const int32_t q = (int32_t)(q_begin + row);
+        if (threadIdx.x == 0) s_state = uf_ld(rep + q);
+        __syncthreads();  // also: the table is staged
+        const int32_t st = s_state;
+        if (st < 0 || count) {  // workgroup-uniform
+            const bool open = st < 0;
+            const uint32_t *p = blk + (size_t)row * (size_t)n;
+            const int64_t lim = q;  // q < n
+            const int64_t head = min(lim, (int64_t)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
+            const int64_t nvec = (lim - head) >> 2;
+            uint64_t best = ~0ull;
+            uint32_t flags = 0;
+            auto entry = [&](int64_t r, uint32_t v) {
+                if (select_pass(v, tab, s)) {
+                    c += count ? 1 : 0;
+                    if (open) greedy_entry(rep, (int32_t)r, v, q_begin, best, flags, err);
+                }
+            };
+            if ((int64_t)threadIdx.x < head) entry(threadIdx.x, p[threadIdx.x]);
+            const uint4 *pv = reinterpret_cast<const uint4 *>(p + head);
+            for (int64_t i = threadIdx.x; i < nvec; i += kThreads) {
+                const uint4 v = pv[i];
+                const int64_t r = head + 4 * i;
+                entry(r, v.x);
+                entry(r + 1, v.y);
+                entry(r + 2, v.z);
+                entry(r + 3, v.w);
+            }
+            const int64_t tail = head + 4 * nvec + threadIdx.x;  // fewer than 4 entries are left
+            if (tail < lim) entry(tail, p[tail]);
+            if (open) {  // workgroup-uniform
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    best = gr_min(best, __shfl_xor((unsigned long long)best, d, 64));
+                    flags |= __shfl_xor(flags, d, 64);
+                }
+                if ((threadIdx.x & 63) == 0) {
+                    ws_best[threadIdx.x >> 6] = best;
+                    ws_flags[threadIdx.x >> 6] = flags;
+                }
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    for (int w = 1; w < kWaves; w++) {
+                        best = gr_min(best, ws_best[w]);
+                        flags |= ws_flags[w];
+                    }
+                    const int32_t now = greedy_decide(q, best, flags);
+                    if (now != st) __hip_atomic_store(rep + q, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    n_left += now < 0 ? 1 : 0;
+                }
+            }
+        }
+        __syncthreads();  // s_state and the waves' words are read
+    }
+    if (threadIdx.x == 0 && n_left) atomicAdd(left, n_left);
+    if (!count) return;  // workgroup-uniform
+    // the passing pairs of this workgroup: one integer atomic, so the total does not depend on order
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < kWaves; w++) t += ws[w];
+        if (t) atomicAdd(n_links, t);
+    }
+}
+
+// One round over a CSR whose rows are short: one wave per row, wave w of the grid takes the rows
+// w, w + the grid's waves, ...  Every entry is a passing pair; one outside [0, q) sets the error
+// word and is not followed.
+__global__ __launch_bounds__(kThreads) void greedy_edges_kernel(const int64_t *__restrict__ row_off, int64_t n_rows,
+                                                                int64_t q_begin, const int32_t *__restrict__ ref_idx,
+                                                                const uint32_t *__restrict__ val, int count,
+                                                                int32_t *__restrict__ rep,
+                                                                unsigned long long *__restrict__ n_links,
+                                                                int32_t *__restrict__ left, int32_t *__restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int64_t n_waves = (int64_t)gridDim.x * kWaves;
+    int32_t n_left = 0;  // lane 0's
+    for (int64_t row = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); row < n_rows; row += n_waves) {  // wave-uniform
+        const int32_t q = (int32_t)(q_begin + row);
+        const int32_t st = __shfl(lane == 0 ? uf_ld(rep + q) : 0, 0, 64);
+        if (st >= 0) continue;  // wave-uniform
+        const int64_t e1 = row_off[row + 1];
+        uint64_t best = ~0ull;
+        uint32_t flags = 0;
+        for (int64_t e = row_off[row] + lane; e < e1; e += 64) {
+            const int32_t r = ref_idx[e];
+            if (r < 0 || r >= q)
+                __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                greedy_entry(rep, r, val[e], q_begin, best, flags, err);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            best = gr_min(best, __shfl_xor((unsigned long long)best, d, 64));
+            flags |= __shfl_xor(flags, d, 64);
+        }
+        if (lane == 0) {
+            const int32_t now = greedy_decide(q, best, flags);
+            if (now != st) __hip_atomic_store(rep + q, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            n_left += now < 0 ? 1 : 0;
+        }
+    }
+    if (lane == 0 && n_left) atomicAdd(left, n_left);
+    // the entry count is the CSR's span: one integer atomic per call
+    if (count && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t t = row_off[n_rows] - row_off[0];
+        if (t > 0) atomicAdd(n_links, (unsigned long long)t);
+    }
+}
+
 // ---- sparse dist (hymet_mash_dist_sparse; DESIGN.md §3 "Sparse dist")
 // A posting is (hash, id): ids are the references first, then the queries of the row range
 // (SpSide::first_q = n_ref); in tri mode the sketches [0, q_end) once each, a sketch being a
@@ -634,6 +819,51 @@ int check_offsets(hymet_ctx *ctx, const int64_t *d_off, int64_t n, int64_t n_has
     return HYMET_OK;
 }
 
+// rounds queued between two reads of the undecided count (HYMET_GREEDY_BATCH; DESIGN.md §3
+// "Greedy derep"): a round over a decided range only reads its state words
+constexpr int kGreedyBatch = 4, kGreedyMaxBatch = 16;
+
+// The rounds of one greedy call over n_rows rows: round(count, d_left) queues one launch that
+// adds the rows it leaves undecided to *d_left.  Ends with the first round that leaves none, and
+// after n_rows + 1 rounds at the latest (then with an error: greedy_entry's argument bounds them).
+template <typename Round>
+int greedy_rounds(hymet_ctx *ctx, const char *what, int64_t n_rows, int32_t *rounds, Round round) {
+    hipStream_t st = ctx->stream;
+    const int batch = (int)hymet::env_int("HYMET_GREEDY_BATCH", kGreedyBatch, 1, kGreedyMaxBatch);
+    int32_t *err = ctx->dctr + hymet::mm::kCtrGreedyErr;
+    hymet::mm::DevBuf left;
+    HY_HIP(left.alloc(4 * kGreedyMaxBatch, st));
+    const int64_t bound = n_rows + 1;
+    int64_t done = 0;
+    while (done < bound) {
+        const int nb = (int)std::min<int64_t>(batch, bound - done);
+        HY_HIP(hipMemsetAsync(left.p, 0, 4 * kGreedyMaxBatch, st));
+        for (int b = 0; b < nb; b++) {
+            const int rc = round(done + b == 0 ? 1 : 0, left.as<int32_t>() + b);
+            if (rc) return rc;
+        }
+        int32_t h_left[kGreedyMaxBatch], bad = 0;
+        HY_HIP(hipMemcpyAsync(h_left, left.p, 4 * (size_t)nb, hipMemcpyDeviceToHost, st));
+        HY_HIP(hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
+        HY_HIP(hipStreamSynchronize(st));
+        if (bad) {
+            *rounds = (int32_t)std::min<int64_t>(done + nb, 0x7fffffff);
+            HY_HIP(hipMemsetAsync(err, 0, 4, st));  // left zeroed for the next call
+            return hymet::fail(HYMET_E_ARG, std::string(what) + ": a passing row before the range is undecided, or a CSR "
+                                                                "index lies outside [0, q)");
+        }
+        for (int b = 0; b < nb; b++) {
+            done++;
+            if (h_left[b] == 0) {
+                *rounds = (int32_t)std::min<int64_t>(done, 0x7fffffff);
+                return HYMET_OK;
+            }
+        }
+    }
+    *rounds = (int32_t)std::min<int64_t>(done, 0x7fffffff);
+    return hymet::fail(HYMET_E_INTERNAL, std::string(what) + ": rows left undecided after n_rows + 1 rounds");
+}
+
 }  // namespace
 
 extern "C" {
@@ -814,6 +1044,55 @@ int hymet_mash_link_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_ro
                        ctx->dctr + hymet::mm::kCtrUfErr);
     HY_CHECK_LAUNCH("link_edges_kernel");
     return HYMET_OK;
+}
+
+int hymet_mash_greedy(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n, int64_t q_begin,
+                      const uint16_t *d_min_common, int32_t s, int32_t *d_rep, uint64_t *d_n_links, int32_t *rounds) {
+    HY_ARG(ctx && rounds, "hymet_mash_greedy: null argument");
+    *rounds = 0;
+    HY_ARG(s >= 1 && s <= kMaxS, "hymet_mash_greedy: sketch size must be in 1.." + std::to_string(kMaxS));
+    HY_ARG(n >= 0 && n < (1ll << 31), "hymet_mash_greedy: n outside [0, 2^31)");
+    HY_ARG(n_rows >= 0 && q_begin >= 0 && q_begin <= n && n_rows <= n - q_begin, "hymet_mash_greedy: rows outside [0, n]");
+    HY_ARG(d_min_common && d_n_links, "hymet_mash_greedy: null argument");
+    HY_HIP(hipSetDevice(ctx->device));
+    if (n_rows == 0) return HYMET_OK;
+    HY_ARG(d_block && d_rep, "hymet_mash_greedy: null argument");
+    HY_ARG((reinterpret_cast<uintptr_t>(d_block) & 3) == 0, "hymet_mash_greedy: block not 4-byte aligned");
+    const double tri =
+        0.5 * ((double)(q_begin + n_rows) * (double)(q_begin + n_rows - 1) - (double)q_begin * (double)(q_begin - 1));
+    const int64_t nb = std::min<int64_t>(n_rows, (int64_t)ctx->n_cu * 8);
+    hymet::ProfScope _ps(ctx, "mash_greedy", 4.0 * tri);  // the first round's; a later one reads its open rows
+    return greedy_rounds(ctx, "hymet_mash_greedy", n_rows, rounds, [&](int count, int32_t *d_left) -> int {
+        hipLaunchKernelGGL(greedy_kernel, dim3((unsigned)nb), dim3(kThreads), 2 * ((size_t)s + 1), ctx->stream, d_block, n_rows,
+                           n, q_begin, d_min_common, (int)s, count, d_rep, reinterpret_cast<unsigned long long *>(d_n_links),
+                           d_left, ctx->dctr + hymet::mm::kCtrGreedyErr);
+        HY_CHECK_LAUNCH("greedy_kernel");
+        return HYMET_OK;
+    });
+}
+
+int hymet_mash_greedy_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_rows, int64_t q_begin,
+                            const int32_t *d_ref_idx, const uint32_t *d_val, int32_t s, int32_t *d_rep,
+                            uint64_t *d_n_links, int32_t *rounds) {
+    HY_ARG(ctx && rounds, "hymet_mash_greedy_edges: null argument");
+    *rounds = 0;
+    HY_ARG(s >= 1 && s <= kMaxS, "hymet_mash_greedy_edges: sketch size must be in 1.." + std::to_string(kMaxS));
+    HY_ARG(n_rows >= 0 && q_begin >= 0 && q_begin < (1ll << 31) && n_rows < (1ll << 31) - q_begin,
+           "hymet_mash_greedy_edges: rows outside [0, 2^31)");
+    HY_ARG(d_n_links, "hymet_mash_greedy_edges: null argument");
+    HY_HIP(hipSetDevice(ctx->device));
+    if (n_rows == 0) return HYMET_OK;
+    HY_ARG(d_row_off && d_ref_idx && d_val && d_rep, "hymet_mash_greedy_edges: null argument");
+    const int64_t nb = std::min<int64_t>(hymet::cdiv(n_rows, kWaves), (int64_t)ctx->n_cu * 8);
+    // the entries are not known here: two offsets and a state word per row of the first round
+    hymet::ProfScope _ps(ctx, "mash_greedy_edges", 20.0 * (double)n_rows);
+    return greedy_rounds(ctx, "hymet_mash_greedy_edges", n_rows, rounds, [&](int count, int32_t *d_left) -> int {
+        hipLaunchKernelGGL(greedy_edges_kernel, dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, d_row_off, n_rows, q_begin,
+                           d_ref_idx, d_val, count, d_rep, reinterpret_cast<unsigned long long *>(d_n_links), d_left,
+                           ctx->dctr + hymet::mm::kCtrGreedyErr);
+        HY_CHECK_LAUNCH("greedy_edges_kernel");
+        return HYMET_OK;
+    });
 }
 
 int hymet_mash_dist_sparse(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t n_ref_hashes, const int64_t *d_ref_off,

@@ -33,6 +33,7 @@
 // stage more.  The chunk kernel tests an entry against the cut's own (common, denom, position)
 // by cross-multiplication and divides only in a wave that stages something: the test is the key
 // comparison exactly, because equal ranks mean equal fractions.
+#include "mash_rank.hpp"
 #include "mm_common.hpp"
 
 #include <algorithm>
@@ -71,15 +72,9 @@ __device__ __forceinline__ void topk_init(const TopK &T) {
     __syncthreads();
 }
 
-// the key of entry (common c, denom d) at position pos: c <= d <= 2^14
+// the key of entry (common c, denom d) at position pos: c <= d <= 2^14 (mash_rank.hpp)
 __device__ __forceinline__ uint64_t topk_key(uint32_t c, uint32_t d, uint32_t pos) {
-    uint32_t rank = 0;
-    if (d != 0) {
-        // floor(c * 2^31 / d) in two 32-bit divisions: c << 17 <= 2^31, the remainder is below 2^14
-        const uint32_t hi = c << 17, q1 = hi / d, r1 = hi - q1 * d;
-        rank = 0x80000000u - ((q1 << 14) + ((r1 << 14) / d));
-    }
-    return (uint64_t)rank << 32 | pos;
+    return hymet::mash_rank_key(c, d, pos);
 }
 
 // Stage key for every lane of the ballot m (the lanes with acc set, m != 0).  Every lane of the

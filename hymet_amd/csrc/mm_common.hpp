@@ -122,6 +122,9 @@ enum : int { kCtrQClass = 0, kCtrGroups = 16, kCtrGClass = 24, kCtrScan = 40, kC
 // the union-find's error word (mash_dist.hip): set by a link or labels kernel that met a parent
 // outside [0, x], read and zeroed again by hymet_mash_labels
 enum : int { kCtrUfErr = 48 };
+// the greedy selection's error word (mash_dist.hip): set by a round that met an undecided row
+// before its range or a CSR index outside [0, q), read and zeroed again by the call that ran it
+enum : int { kCtrGreedyErr = 49 };
 
 // Called by every thread of every block after the block's last update of cnt[0, n): the last
 // block to arrive stores the totals into the mailbox words mail[0, n) and zeroes the counters

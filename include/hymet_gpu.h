@@ -354,6 +354,38 @@ int hymet_mash_dist_sparse(hymet_ctx *ctx, const uint64_t *d_ref_hashes, int64_t
  * every index must lie inside d_parent.  Queued on the context's stream. */
 int hymet_mash_link_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_rows, int64_t q_begin,
                           const int32_t *d_ref_idx, int32_t *d_parent, uint64_t *d_n_links);
+/* Greedy dereplication of the n sketches of one DB, numbered in priority order (the host permutes
+ * the DB): walking them in that order, a sketch is a representative iff no earlier representative
+ * passes with it (hymet_mash_link's filter: denom <= s and common >= d_min_common[denom]);
+ * otherwise it is a member of the nearest of the earlier representatives that pass with it, in
+ * hymet_mash_dist_topk's order (the exact rational common / denom, descending, 0 / 0 counting as
+ * 1; common > denom counts as 1 too), equal rationals going to the smaller index.  So every
+ * member passes with its representative, no two representatives pass with each other, and the
+ * result is unique: it depends neither on the row blocks, nor on the grid, nor on the order in
+ * which the state words are stored.
+ * d_block, n_rows, n, q_begin, d_min_common, s and *d_n_links (the passing entries r < q, one
+ * integer atomic per workgroup) are hymet_mash_link's.  d_rep is an int32[n] the caller fills
+ * with -1 before the first call; on return every row of [q_begin, q_begin + n_rows) holds its own
+ * index (a representative) or its representative's.  The calls over one DB must cover ascending,
+ * contiguous row ranges: a passing entry r < q_begin that no earlier call decided is reported as
+ * HYMET_E_ARG through an error word of the context, which the call clears again (the range's
+ * rows then hold no result).  A call runs rounds, one launch each, in which every undecided row
+ * reads its passing neighbours' states, until its range is decided; *rounds (a host word) is
+ * their number, at most n_rows + 1 (HYMET_E_INTERNAL beyond, never a longer loop).
+ * HYMET_GREEDY_BATCH (1..16) in the environment: the rounds queued between two reads of the
+ * undecided count.  Synchronises. */
+int hymet_mash_greedy(hymet_ctx *ctx, const uint32_t *d_block, int64_t n_rows, int64_t n, int64_t q_begin,
+                      const uint16_t *d_min_common, int32_t s, int32_t *d_rep, uint64_t *d_n_links, int32_t *rounds);
+/* hymet_mash_greedy over a CSR instead of a dense block (d_row_off: n_rows + 1 int64, then
+ * reference index and packed value per entry, as hymet_mash_dist_sparse with tri != 0 or
+ * hymet_mash_dist_select leaves it on the device): every entry of row `row` is a passing pair of
+ * q = q_begin + row, its index in [0, q) (any other index: HYMET_E_ARG, as above; it is not
+ * followed).  Adds the entry count to *d_n_links.  d_rep (which must hold q_begin + n_rows
+ * words), *rounds, the order of the calls and the result are hymet_mash_greedy's: dense and CSR
+ * calls may alternate over the row ranges of one DB.  Synchronises. */
+int hymet_mash_greedy_edges(hymet_ctx *ctx, const int64_t *d_row_off, int64_t n_rows, int64_t q_begin,
+                            const int32_t *d_ref_idx, const uint32_t *d_val, int32_t s, int32_t *d_rep,
+                            uint64_t *d_n_links, int32_t *rounds);
 /* Nearest references (`dist --top K`): the K best entries of every row of a dist result.
  * Order: nearest first by the exact rational common / denom, descending, with 0 / 0 counting as 1
  * (its distance is 0); equal rationals, 1/2 and 500/1000 for example, by reference index,
