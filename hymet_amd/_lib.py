@@ -59,6 +59,11 @@ _SIGS = {
                                     _vp]),
     "hymet_sketch_counted_max_size": (_i32, []),
     "hymet_sketch_counted_tune": (_i32, [_i32]),
+    "hymet_sketch_stream_create": (_i32, [_vp, _i32, _u32, _i32, _i32, _i64, _c.POINTER(_vp)]),
+    "hymet_sketch_stream_add": (_i32, [_vp, _vp, _vp, _i64, _i64]),
+    "hymet_sketch_stream_end_pass": (_i32, [_vp, _c.POINTER(_i32)]),
+    "hymet_sketch_stream_result": (_i32, [_vp, _vp, _vp, _c.POINTER(_i32), _vp]),
+    "hymet_sketch_stream_destroy": (_i32, [_vp]),
     "hymet_mash_dist": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "hymet_mash_dist_tile": (_i32, [_i32]),
     "hymet_mash_dist_tune": (_i32, [_i32, _i32]),

@@ -23,13 +23,15 @@
         == scripts/downloadDB.py:178-249 offline (detailed_taxonomy.tsv, combined_genomes.fasta)
     python -m hymet_amd.cli eval-cami [--pred-profile ... --outdir D]
         == tools/eval_cami.py (CAMI profile and contig metrics)
-    python -m hymet_amd.cli sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] -o PREFIX FILE...
+    python -m hymet_amd.cli sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] [--batch-bases SIZE] -o PREFIX FILE...
         == mash sketch (builds the sketch DB the screen reads; the reference downloads its DBs,
            so there is no stage script and no scripts/ wrapper for it).  FILE is FASTA or FASTQ;
-           -r: each FILE is a read set, -m M: keep only k-mers seen at least M times
-    python -m hymet_amd.cli dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] REF.msh QUERY...
+           -r: each FILE is a read set, -m M: keep only k-mers seen at least M times;
+           --batch-bases SIZE: bases read and held per batch, a read file above it is streamed
+    python -m hymet_amd.cli dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] [--batch-bases SIZE] REF.msh QUERY...
         == mash dist (all-pairs distances between sketch DBs; QUERY is .msh, FASTA or FASTQ,
-           with -r / -m M a read set; like sketch, not a stage of the reference workflow)
+           with -r / -m M a read set, --batch-bases SIZE as for sketch; like sketch, not a stage
+           of the reference workflow)
     python -m hymet_amd.cli mash-screen [-w] [-i MIN_IDENTITY] [-v MAX_P] DB.msh FILE...
         == mash screen (the rows on stdout, in sketch order; -w: winner-take-all; FILE is FASTA
            or FASTQ)
@@ -334,7 +336,7 @@ def cmd_download_db(argv: Sequence[str]) -> int:
 
 
 # ------------------------------------------------------------------ sketch (mash sketch)
-SKETCH_USAGE = "usage: sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] -o PREFIX FILE..."
+SKETCH_USAGE = "usage: sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] [--batch-bases SIZE] -o PREFIX FILE..."
 
 
 def parse_size(text: str) -> int:
@@ -349,8 +351,9 @@ def parse_size(text: str) -> int:
 
 def sketch_args(argv: Sequence[str]):
     """`mash sketch`'s flag letters.  Returns the parsed namespace, or None after printing the
-    usage line (unknown flag, -n, no -o, no FILE, -m below 1, -r or -m above 1 with -i, a -g that
-    is no size).  a.reads is set by -r and by -m above 1."""
+    usage line (unknown flag, -n, no -o, no FILE, -m below 1, -r or -m above 1 with -i, a -g or
+    --batch-bases that is no size).  a.reads is set by -r and by -m above 1, a.batch_bases is
+    sketch.DEFAULT_BATCH_BASES unless --batch-bases gives it."""
     class _Parser(argparse.ArgumentParser):
         def error(self, message):
             raise ValueError(message)
@@ -366,6 +369,7 @@ def sketch_args(argv: Sequence[str]):
     p.add_argument("-r", action="store_true", dest="reads")
     p.add_argument("-m", type=int, default=1, dest="min_copies")
     p.add_argument("-g", type=parse_size, default=None, dest="genome_size")
+    p.add_argument("--batch-bases", type=parse_size, default=None, dest="batch_bases")
     p.add_argument("-o", dest="out")
     p.add_argument("-h", action="store_true", dest="help")
     p.add_argument("files", nargs="*")
@@ -381,6 +385,9 @@ def sketch_args(argv: Sequence[str]):
         a.reads = a.reads or a.min_copies > 1
         if a.reads and a.individual:
             raise ValueError("-r / -m does not go with -i: a read set is one sketch per FILE")
+        if a.batch_bases is None:
+            from .sketch import DEFAULT_BATCH_BASES
+            a.batch_bases = DEFAULT_BATCH_BASES
         if not a.out:
             raise ValueError("-o PREFIX is required")
         if not a.files:
@@ -403,7 +410,7 @@ def expand_lists(files: Sequence[str]) -> List[str]:
 
 
 def cmd_sketch(argv: Sequence[str]) -> int:
-    """mash sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] -o PREFIX FILE...:
+    """mash sketch [-k K] [-s S] [-S SEED] [-i] [-Z] [-l] [-r] [-m M] [-g SIZE] [--batch-bases SIZE] -o PREFIX FILE...:
     sketch each FILE (each record with -i) on the GPU and write PREFIX.msh (the suffix is not
     doubled).  A FILE is FASTA or FASTQ (gzip too).
       -k  k-mer size, 1..32 (21)        -s  sketch size (1000)       -S  hash seed (42)
@@ -412,6 +419,9 @@ def cmd_sketch(argv: Sequence[str]) -> int:
           one stderr line per FILE with that estimate and the estimated coverage
       -m  with -r: keep only k-mers seen at least M times in the FILE (1); M > 1 implies -r
       -g  with -r: the genome size to record instead of the estimate (k / m / g suffix allowed)
+      --batch-bases  bases read and sketched per batch (512 Mi; k / m / g suffix allowed): the
+          host-memory knob.  A read set (-r) larger than this is never held whole: it is read
+          batch by batch and streamed through the GPU, to the same sketch
     Known limits: -n (noncanonical), protein alphabets and the Bloom filter (-b) are not
     supported, -r does not go with -i, and hash lists are always written 64 bits wide, also for
     k <= 16 where Mash writes 32-bit lists (this project's reader widens either form)."""
@@ -428,7 +438,8 @@ def cmd_sketch(argv: Sequence[str]) -> int:
     info = []
     try:
         db = sk.sketch_files(gpu, files, k=a.k, seed=a.seed, s=a.s, individual=a.individual, preserve_case=a.preserve_case,
-                             reads=a.reads, min_copies=a.min_copies, genome_size=a.genome_size, read_info=info)
+                             reads=a.reads, min_copies=a.min_copies, genome_size=a.genome_size, read_info=info,
+                             batch_bases=a.batch_bases)
     except ValueError as e:
         print(f"ERROR: {e}", file=sys.stderr)
         return 1
@@ -443,13 +454,14 @@ def cmd_sketch(argv: Sequence[str]) -> int:
 
 
 # ------------------------------------------------------------------ dist (mash dist)
-DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] REF.msh QUERY..."
+DIST_USAGE = "usage: dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] [--batch-bases SIZE] REF.msh QUERY..."
 
 
 def dist_args(argv: Sequence[str]):
     """`mash dist`'s flag letters.  Returns the parsed namespace, or None after printing the
     usage line (unknown flag, no REF.msh, no QUERY, -m below 1, -r or -m above 1 with -i or with
-    nothing but .msh QUERYs).  a.reads is set by -r and by -m above 1."""
+    nothing but .msh QUERYs, a --batch-bases that is no size).  a.reads is set by -r and by -m
+    above 1, a.batch_bases is sketch.DEFAULT_BATCH_BASES unless --batch-bases gives it."""
     class _Parser(argparse.ArgumentParser):
         def error(self, message):
             raise ValueError(message)
@@ -457,6 +469,7 @@ def dist_args(argv: Sequence[str]):
     p = _Parser(prog="dist", add_help=False, allow_abbrev=False)
     p.add_argument("-r", action="store_true", dest="reads")
     p.add_argument("-m", type=int, default=1, dest="min_copies")
+    p.add_argument("--batch-bases", type=parse_size, default=None, dest="batch_bases")
     p.add_argument("-d", type=float, default=None, dest="max_dist")
     p.add_argument("-v", type=float, default=1.0, dest="max_p")
     p.add_argument("-t", action="store_true", dest="table")
@@ -478,6 +491,9 @@ def dist_args(argv: Sequence[str]):
         if a.min_copies < 1:
             raise ValueError(f"-m {a.min_copies}: the minimum number of copies is at least 1")
         a.reads = a.reads or a.min_copies > 1
+        if a.batch_bases is None:
+            from .sketch import DEFAULT_BATCH_BASES
+            a.batch_bases = DEFAULT_BATCH_BASES
         if a.reads and a.individual:
             raise ValueError("-r / -m does not go with -i: a read set is one sketch per QUERY")
         if a.reads and not a.lists and all(q.endswith(".msh") for q in a.files[1:]):
@@ -510,7 +526,7 @@ def dist_args(argv: Sequence[str]):
 
 
 def cmd_dist(argv: Sequence[str]) -> int:
-    """mash dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] REF.msh QUERY...: the distance of every QUERY
+    """mash dist [-d D] [-v P] [-t] [--sparse] [--top K] [-i] [-l] [-r] [-m M] [--batch-bases SIZE] REF.msh QUERY...: the distance of every QUERY
     sketch to every sketch of REF.msh, computed on the GPU; one row per pair on stdout
     (reference, query, distance, p-value, shared/compared hashes), query-major.
       -d  keep pairs with distance <= D (1)     -v  keep pairs with p-value <= P (1)
@@ -521,6 +537,8 @@ def cmd_dist(argv: Sequence[str]) -> int:
                 equal common/denom ratios in reference order.  Not with -t or -v P < 1.
       -r  each sequence QUERY is a read set (one sketch per QUERY)
       -m  with -r: keep only k-mers seen at least M times in the QUERY (1); M > 1 implies -r
+      --batch-bases  bases of sequence QUERYs read and sketched per batch (512 Mi; k / m / g suffix
+                allowed); a read-set QUERY larger than this is streamed, to the same sketch
     A QUERY ending in .msh is loaded; any other is FASTA or FASTQ (gzip too), sketched on the GPU
     with REF.msh's k-mer size, seed, sketch size and case rule.  -r / -m need such a QUERY."""
     a = dist_args(argv)
@@ -546,7 +564,8 @@ def cmd_dist(argv: Sequence[str]) -> int:
     def flush():      # consecutive FASTA queries are sketched in one call
         if fasta:
             dbs.append(sk.sketch_files(gpu, fasta, k=ref.k, seed=ref.seed, s=ref.sketch_size, individual=a.individual,
-                                       preserve_case=ref.preserve_case, reads=a.reads, min_copies=a.min_copies))
+                                       preserve_case=ref.preserve_case, reads=a.reads, min_copies=a.min_copies,
+                                       batch_bases=a.batch_bases))
             fasta.clear()
 
     try:

@@ -196,6 +196,110 @@ def read_seqs(paths) -> SeqSet:
     return from_records(recs, [str(p) for p in paths], file_of)
 
 
+DEFAULT_BLOCK_BYTES = 1 << 24
+
+
+def _record_batches(recs, pending, batch_bases):
+    """Move recs behind pending (a list of records and its number of bases) and yield a SeqSet
+    whenever the collected records hold batch_bases bases; the cuts are found on the cumulated
+    lengths, not by a loop over the records."""
+    if not recs:
+        return
+    ends = np.cumsum(np.fromiter((len(r[2]) for r in recs), np.int64, len(recs)))
+    done, at = 0, 0                       # records and bases of recs already handed on
+    while True:
+        # the first record with which pending reaches batch_bases
+        j = int(np.searchsorted(ends, at + batch_bases - pending[1], side="left"))
+        if j >= len(recs):
+            break
+        pending[0].extend(recs[done:j + 1])
+        yield from_records(pending[0])
+        pending[0], pending[1] = [], 0
+        done, at = j + 1, int(ends[j])
+    pending[0].extend(recs[done:])
+    pending[1] += int(ends[-1]) - at
+
+
+def iter_seq_batches(path, batch_bases: int, block_bytes: int = DEFAULT_BLOCK_BYTES):
+    """The records of one FASTA or FASTQ file (gzip too) as SeqSets of whole records, in file
+    order: every batch but the last holds at least batch_bases bases -- it is closed by the record
+    that reaches them -- and at least one batch is yielded (an empty one for a file without
+    records).  The file is read in blocks of block_bytes and never held whole: at any time there
+    is one batch being collected plus one block (and the tail of the last block that did not end a
+    record).  The concatenated records are those of read_seqs([path]); the format is decided as
+    there, by the first byte after leading white space.
+
+    FASTA: the text read so far is cut at its last b"\\n>", the piece before it goes through
+    parse_fasta_bytes and the rest waits for the next block.  Every piece but the first starts
+    with '>', a record's lines are never split, and leading junk stays in the first piece, so the
+    pieces' records are the whole text's.
+
+    FASTQ: '\\r' is dropped as parse_fastq_bytes drops it, and the text is cut at the last line
+    break whose line index from the start of the file is a multiple of four.  A piece is accepted
+    only if it has the strict four-line shape (_fastq_four_lines: '@' line, a sequence line not
+    starting with '+', '+' line, a quality line of the sequence's length).  Why the pieces
+    together are kseq's parse of the whole text: kseq is at a record boundary at the start of the
+    file; on a text of the strict shape it reads, per four lines, the header, one sequence line
+    (the next line starts with '+'), the '+' line and one quality line (its length reaches the
+    sequence's at once), so after a piece that passes the check it stands at a record boundary
+    again, exactly at the piece's end -- a multiple of four lines from the file's start, where
+    the next piece begins.  By induction every accepted piece is parsed as kseq parses that
+    stretch of the whole text, '@' or '>' at the start of a quality line included.
+    A piece that is not of that shape (wrapped sequences, leading blank lines, a truncated tail)
+    ends the streaming: it and the rest of the file go through parse_fastq_bytes -- kseq's rules
+    from a record boundary on -- and are yielded, with the records still waiting, as one last
+    batch.  When the first piece already fails, that is the whole file as one batch, read_seqs'
+    behaviour; a wrapped FASTQ is therefore not streamed (out of scope).  A truncated file raises
+    parse_fastq_bytes' ValueError."""
+    import re
+    batch_bases = max(1, int(batch_bases))
+    block_bytes = max(1, int(block_bytes))
+    pending = [[], 0]
+    n_out = 0
+    with _open(path) as f:
+        buf = b""
+        fastq = None
+        while fastq is None:              # the first byte after leading white space decides
+            block = f.read(block_bytes)
+            buf += block
+            m = re.search(rb"\S", buf)
+            if m is not None:
+                fastq = buf[m.start():m.start() + 1] == b"@"
+            elif not block:
+                fastq = False
+        if fastq:
+            buf = buf.replace(b"\r", b"")
+        eof = False
+        while not eof:
+            block = f.read(block_bytes)
+            eof = not block
+            if fastq:
+                buf += block.replace(b"\r", b"")
+                if eof:
+                    if buf and not buf.endswith(b"\n"):
+                        buf += b"\n"
+                    cut = len(buf)
+                else:
+                    nl = np.flatnonzero(np.frombuffer(buf, dtype=np.uint8) == 10)
+                    cut = int(nl[len(nl) // 4 * 4 - 1]) + 1 if len(nl) >= 4 else 0
+                piece = buf[:cut]
+                recs = _fastq_four_lines(piece) if piece else []
+                if recs is None:          # not the strict shape: the general rules for all that is left
+                    pending[0].extend(parse_fastq_bytes(piece + buf[cut:] + f.read()))
+                    break
+                buf = b"" if eof else buf[cut:]
+            else:
+                buf += block
+                cut = len(buf) if eof else buf.rfind(b"\n>") + 1
+                recs = parse_fasta_bytes(buf[:cut]) if cut else []
+                buf = buf[cut:]
+            for ss in _record_batches(recs, pending, batch_bases):
+                n_out += 1
+                yield ss
+    if pending[0] or n_out == 0:
+        yield from_records(pending[0])
+
+
 class DevicePool:
     """A SeqSet resident in HBM, packed for one alphabet (hymet_pack)."""
 

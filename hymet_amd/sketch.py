@@ -30,6 +30,12 @@ from .msh import SketchDB
 DEFAULT_CHUNK_BASES = 1 << 20
 # bases per batch of sketch_files: the ASCII pool on the host and in HBM, then 0.375 B per base
 DEFAULT_BATCH_BASES = 1 << 29
+# the streamed read-set sketch (sketch_stream).  max_live: 2^28 (hash, count) pairs are 3 GiB, and
+# the merge writes a second list beside the first; chosen from memory, not measured.  slice_bases:
+# k-mer starts per slice, chosen among 2^20, 2^22, 2^24 and 2^26 by tools/sketch_stream_bench.py
+# (DESIGN.md §3 "Sketch: read sets, streamed")
+DEFAULT_STREAM_MAX_LIVE = 1 << 28
+DEFAULT_STREAM_SLICE_BASES = 1 << 26
 # output rows per batch of sketch_files are capped so that rows x s x 8 B stays under this
 _MAX_OUT_BYTES = 1 << 30
 
@@ -167,6 +173,55 @@ def sketch_pool_counted(gpu, pool, group_of, k: int, seed: int, s: int, min_copi
 sketch_pool_counted.stats = {"passes": 0, "merged": 0}
 
 
+def sketch_stream(gpu, batches, k: int, seed: int, s: int, min_copies: int, max_live: Optional[int] = None,
+                  slice_bases: Optional[int] = None, alphabet: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Mash `sketch -r -m M` of ONE read set given as batches: (hashes np.uint64, counts np.uint32),
+    what sketch_pool_counted returns for the batches' records as one group, whatever the batches,
+    slice_bases and max_live (csrc/sketch_stream.hip).  batches: a re-iterable of seqio.SeqSets
+    of whole records (a list, or an object whose __iter__ reads the file again): each is packed
+    (DevicePool, alphabet: DevicePool.ALPHA_MASH by default) and fed, one at a time in HBM, and the
+    whole sequence is fed again for every further pass the device asks for.  max_live: (hash,
+    count) pairs the window may hold between slices (DEFAULT_STREAM_MAX_LIVE); slice_bases: k-mer
+    starts per slice (DEFAULT_STREAM_SLICE_BASES).  The counts saturate at 2^32 - 1; there is no
+    limit on the read set's size.  sketch_stream.stats holds what the call did: {"passes",
+    "slices", "emitted" (candidate hashes written), "max_live" (the most pairs the window held)}."""
+    from ._lib import check
+    from .seqio import DevicePool
+    torch = gpu.torch
+    lib = gpu.lib
+    s = int(s)
+    alphabet = DevicePool.ALPHA_MASH if alphabet is None else alphabet
+    sketch_stream.stats = {"passes": 0, "slices": 0, "emitted": 0, "max_live": 0}
+    h = ctypes.c_void_p()
+    check(lib.hymet_sketch_stream_create(gpu.ctx, int(k), int(seed), s, int(min_copies),
+                                         int(max_live or DEFAULT_STREAM_MAX_LIVE), ctypes.byref(h)),
+          "hymet_sketch_stream_create")
+    try:
+        more = ctypes.c_int32(1)
+        while more.value:
+            for ss in batches:
+                pool = DevicePool(gpu, ss, alphabet)
+                check(lib.hymet_sketch_stream_add(h, ptr(pool.w2b), ptr(pool.wmask), pool.n_bases,
+                                                  int(slice_bases or DEFAULT_STREAM_SLICE_BASES)), "hymet_sketch_stream_add")
+                del pool
+            check(lib.hymet_sketch_stream_end_pass(h, ctypes.byref(more)), "hymet_sketch_stream_end_pass")
+        # one buffer, one copy: the row (8 B per entry), then its multiplicities (4 B)
+        out = gpu.empty(s + (s + 1) // 2, torch.int64)
+        n = ctypes.c_int32()
+        stats = (ctypes.c_int64 * 4)()
+        check(lib.hymet_sketch_stream_result(h, ptr(out), ctypes.c_void_p(out.data_ptr() + 8 * s), ctypes.byref(n),
+                                             ctypes.cast(stats, ctypes.c_void_p)), "hymet_sketch_stream_result")
+    finally:
+        lib.hymet_sketch_stream_destroy(h)
+    sketch_stream.stats = {"passes": int(stats[0]), "slices": int(stats[1]), "emitted": int(stats[2]),
+                           "max_live": int(stats[3])}
+    host = out.cpu().numpy()
+    return host[:s].view(np.uint64)[:n.value], host[s:].view(np.uint32)[:n.value]
+
+
+sketch_stream.stats = {"passes": 0, "slices": 0, "emitted": 0, "max_live": 0}
+
+
 # ------------------------------------------------------------------ metadata (unpinned)
 def read_set_length(hashes, s: int, k: int, genome_size: Optional[int] = None) -> int:
     """The `length` a read-set sketch carries in the .msh -- this project's rule, restating
@@ -196,12 +251,59 @@ def file_meta(path: str, names: Sequence[str], comments: Sequence[str], lengths:
     summed lengths of the records of >= k bases; comment = "<first name> <first comment>" for
     one such record, "[N seqs] <first name> <first comment> [...]" for N > 1.  Unpinned (module
     docstring)."""
-    ok = [i for i, L in enumerate(lengths) if int(L) >= k]
-    if not ok:
-        return None
-    head = _join(names[ok[0]], comments[ok[0]])
-    comment = head if len(ok) == 1 else f"[{len(ok)} seqs] {head} [...]"
-    return str(path), comment, int(sum(int(lengths[i]) for i in ok))
+    acc = FileMetaAcc(k)
+    acc.add(names, comments, lengths)
+    return acc.meta(path)
+
+
+class FileMetaAcc:
+    """file_meta's inputs collected over the batches of one file: the first record of >= k bases,
+    the number of such records and their summed length."""
+
+    def __init__(self, k: int):
+        self.k = int(k)
+        self.first: Optional[Tuple[str, str]] = None
+        self.n = 0
+        self.total = 0
+
+    def add(self, names: Sequence[str], comments: Sequence[str], lengths: Sequence[int]):
+        ok = [i for i, L in enumerate(lengths) if int(L) >= self.k]
+        if ok and self.first is None:
+            self.first = (names[ok[0]], comments[ok[0]])
+        self.n += len(ok)
+        self.total += int(sum(int(lengths[i]) for i in ok))
+
+    def meta(self, path: str) -> Optional[Tuple[str, str, int]]:
+        if self.first is None:
+            return None
+        head = _join(*self.first)
+        comment = head if self.n == 1 else f"[{self.n} seqs] {head} [...]"
+        return str(path), comment, self.total
+
+
+class _FileBatches:
+    """The batches of one read file as sketch_stream's re-iterable: the first iteration hands on
+    the batches already read and goes on with the open reader, collecting file_meta's inputs on
+    the way; every later one reads the file again."""
+
+    def __init__(self, path, batch_bases: int, head, rest, k: int):
+        self.path, self.batch_bases = path, batch_bases
+        self.head, self.rest = head, rest
+        self.acc = FileMetaAcc(k)
+
+    def __iter__(self):
+        if self.rest is None:
+            from .seqio import iter_seq_batches
+            yield from iter_seq_batches(self.path, self.batch_bases)
+            return
+        head, rest, self.head, self.rest = self.head, self.rest, None, None
+        while head:
+            ss = head.pop(0)
+            self.acc.add(ss.names, ss.comments, ss.lengths)
+            yield ss
+        for ss in rest:
+            self.acc.add(ss.names, ss.comments, ss.lengths)
+            yield ss
 
 
 def _warn(msg: str):
@@ -216,7 +318,7 @@ def sketch_files(gpu, paths: Sequence[str], k: int = 21, seed: int = 42, s: int 
     references in argument order.  The files are FASTA or FASTQ (gzip too, seqio.read_seqs) and
     are sketched in batches of about batch_bases bases -- read, pack (DevicePool), sketch_pool --
     so neither the host nor HBM ever holds the whole collection; one file is the smallest unit of
-    a batch.
+    a batch, except a read file larger than a batch (below).
 
     File mode: one reference per file (file_meta); a file with no record of k bases is skipped
     with a warning.  individual (`-i`): one reference per record, named and commented as the
@@ -229,8 +331,11 @@ def sketch_files(gpu, paths: Sequence[str], k: int = 21, seed: int = 42, s: int 
     rule (read_set_length): genome_size (`-g`) if given, else the genome-size estimate of a full
     row, else the number of hashes.  The multiplicities are not written to the .msh; read_info,
     when a list, receives per sketch (name, length, mean multiplicity of the kept hashes -- the
-    estimated coverage).  Not with individual (ValueError)."""
-    from .seqio import DevicePool, from_records, read_seqs
+    estimated coverage).  Not with individual (ValueError).  A read file is read in batches of
+    batch_bases bases (seqio.iter_seq_batches): one that ends within its first batch goes the way
+    described above, grouped with its neighbours; a larger one is never held whole -- it is
+    streamed through sketch_stream, batch by batch, to the same row, name, comment and length."""
+    from .seqio import DevicePool, from_records, iter_seq_batches, read_seqs
     if not 1 <= int(k) <= 32:
         raise ValueError(f"k={k}: Mash k-mer sizes are 1..32")
     if int(min_copies) < 1:
@@ -273,8 +378,35 @@ def sketch_files(gpu, paths: Sequence[str], k: int = 21, seed: int = 42, s: int 
                 hashes.append(h)
         recs, group_of, meta, bases = [], [], [], 0
 
+    def stream(p, head, rest):
+        """A read file of more than one batch: sketched on its own, batch by batch."""
+        fb = _FileBatches(p, batch_bases, head, rest, k)
+        h, c = sketch_stream(gpu, fb, k, seed, s, int(min_copies), alphabet=alpha)
+        m = fb.acc.meta(str(p))
+        if m is None:
+            _warn(f"Skipping {p}: no sequence of at least {k} bases.")
+            return
+        ln = min(read_set_length(h, s, k, genome_size), (1 << 63) - 1)
+        if read_info is not None:
+            read_info.append((m[0], ln, float(c.mean()) if len(c) else 0.0))
+        names.append(m[0])
+        comments.append(m[1])
+        lengths.append(ln)
+        hashes.append(h)
+
     for p in paths:
-        ss = read_seqs([p])
+        if reads:
+            it = iter_seq_batches(p, batch_bases)
+            ss = next(it)
+            second = next(it, None)
+            if second is not None:       # larger than one batch: the pending files first, to keep the order
+                flush()
+                head = [ss, second]
+                ss = second = None
+                stream(p, head, it)
+                continue
+        else:
+            ss = read_seqs([p])
         if individual:
             for i in range(ss.n):
                 L = int(ss.lengths[i])

@@ -259,6 +259,29 @@ int hymet_sketch_counted_max_size(void);
  * hymet_sketch_counted_max_size().  It changes the number of passes, never the result.  Process-
  * wide; for tests and timing only, like hymet_mash_topk_tune. */
 int hymet_sketch_counted_tune(int keep);
+/* The same sketch of a read set fed in batches (a file larger than one batch): one handle per read
+ * set, the row and a window of (hash, count) pairs kept in HBM between the calls.  create: k in
+ * 1..32, s in 1..hymet_sketch_counted_max_size(), min_copies >= 1, max_live >= 2 (the pairs the
+ * window may hold after a slice; a smaller value costs passes, never the result).  add: one packed
+ * pool of whole records (hymet_pack's layout, hymet_sketch_batch's hashing), cut into slices of
+ * at most slice_bases >= 1 k-mer starts (shorter ones at the start of a pass, while every hash is
+ * still a candidate); it returns with the stream idle; refused once the read set is finished.  end_pass: after the last batch of the file; *need_more = 1 when every batch must be
+ * fed again in the same order (the window was cut and the row is still short), else the read set is
+ * finished.  result (finished read sets only): the row's hashes and multiplicities (saturating at
+ * 2^32 - 1; there is no limit on the number of positions) copied to d_out / d_out_count (room for
+ * s), *n entries; h_stats (nullable, host): [0] passes, [1] slices, [2] candidate hashes emitted,
+ * [3] the largest number of pairs the window held.  The result depends on neither the batches, the
+ * slices, max_live nor the schedule.  All work runs on the stream of the context given to create,
+ * which must outlive the handle. */
+typedef struct hymet_sketch_stream hymet_sketch_stream;
+int hymet_sketch_stream_create(hymet_ctx *ctx, int k, uint32_t seed, int32_t s, int32_t min_copies,
+                               int64_t max_live, hymet_sketch_stream **out);
+int hymet_sketch_stream_add(hymet_sketch_stream *st, const uint32_t *d_2b, const uint32_t *d_mask,
+                            int64_t n_bases, int64_t slice_bases);
+int hymet_sketch_stream_end_pass(hymet_sketch_stream *st, int32_t *need_more);
+int hymet_sketch_stream_result(hymet_sketch_stream *st, uint64_t *d_out, uint32_t *d_out_count, int32_t *n,
+                               int64_t *h_stats);
+int hymet_sketch_stream_destroy(hymet_sketch_stream *st);
 
 /* ------------------------------------------------------------ Mash dist (sketch vs sketch)
  * Replaces `mash dist REF.msh QUERY.msh`: for every (reference, query) pair of two sketch DBs
