@@ -1030,6 +1030,7 @@ int chain_set(hymet_ctx *ctx, const hymet_mm_opt *opt, float pen_gap, float pen_
     }
     int rc = derive_heads(ctx, A);
     if (rc) return rc;
+    C.ax32 = A.ax32.as<uint32_t>();
     Groups Gr;
     rc = build_groups(ctx, A, n_q, Gr);
     if (rc) return rc;

@@ -40,13 +40,13 @@ struct hymet_mm_result {
 namespace hymet {
 namespace mm {
 
-int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint32_t *ay, int span, const int32_t *ids, const int64_t *cfirst,
-                   const uint64_t *cu, const int64_t *cboff,
-                   const int64_t *qc, const int64_t *qb, const uint64_t *mini_pos, const int64_t *mp_off, const int64_t *qlen,
+int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint32_t *ax32, const uint32_t *ay, int span, const int32_t *ids,
+                   const int64_t *cfirst, const uint64_t *cu, const int64_t *cboff,
+                   const int64_t *qc, const int64_t *qb, const int64_t *mp_off, const int64_t *qlen,
                    const uint32_t *name_hash, const int32_t *rep_len, const int64_t *ref_len, int n_q, const hymet_mm_opt *o,
                    int k, void *z, hymet_mm_reg *regs, int32_t *w, uint64_t *cov, int32_t *tmp, int32_t *n_regs,
-                   int64_t NB, int64_t NC, int64_t NM, const uint32_t *cq,
-                   const MiniWord *mtab, const int64_t *qbase, const uint32_t *skip_q, uint64_t *sumk, bool sumk_done);
+                   int64_t NB, int64_t NC, const uint32_t *cq,
+                   const MiniWord *mtab, const int64_t *qbase, const uint32_t *skip_q);
 
 namespace {
 
@@ -963,9 +963,8 @@ static int long_join_anchors(MapBatch &B, const AnchorSet &S1, const LeanJoin &l
     return dump_anchors(ctx, "HYMET_DUMP_ANCHORS2", S2, n_q, dumped);
 }
 
-// 8 regions of one chain set: records at the set's chain offsets (rg) + per-query counts (nr).
-// sumk (per query: the sum of its minimizer spans, avg_k) is computed by the call's first run.
-static int run_regions(MapBatch &B, ChainSet &C, DevBuf &rg, DevBuf &nr, const uint32_t *skip_q, DevBuf &sumk, bool &sumk_done) {
+// 8 regions of one chain set: records at the set's chain offsets (rg) + per-query counts (nr)
+static int run_regions(MapBatch &B, ChainSet &C, DevBuf &rg, DevBuf &nr, const uint32_t *skip_q) {
     hipStream_t st = B.ctx->stream;
     const int64_t NC = C.n_chain;
     DevBuf z, wv, cov, tmp;
@@ -975,13 +974,11 @@ static int run_regions(MapBatch &B, ChainSet &C, DevBuf &rg, DevBuf &nr, const u
     HY_HIP(cov.alloc(8 * (size_t)(NC + 1), st));
     HY_HIP(tmp.alloc(4 * (size_t)(NC + 1), st));
     HY_HIP(nr.alloc(4 * (size_t)B.n_q, st));
-    return launch_regions(B.ctx, C.ax, C.ay, C.span, C.ids.as<int32_t>(), C.cfirst.as<int64_t>(), C.cu.as<uint64_t>(),
-                          C.cboff.as<int64_t>(), C.d_qc.as<int64_t>(), C.d_qb.as<int64_t>(), B.mini_pos.as<uint64_t>(),
-                          B.mp_off.as<int64_t>(), B.d_qlen.as<int64_t>(), B.d_hash, B.rep_len.as<int32_t>(), B.idx->d_len,
+    return launch_regions(B.ctx, C.ax, C.ax32, C.ay, C.span, C.ids.as<int32_t>(), C.cfirst.as<int64_t>(), C.cu.as<uint64_t>(),
+                          C.cboff.as<int64_t>(), C.d_qc.as<int64_t>(), C.d_qb.as<int64_t>(), B.mp_off.as<int64_t>(), B.d_qlen.as<int64_t>(), B.d_hash, B.rep_len.as<int32_t>(), B.idx->d_len,
                           B.n_q, B.opt, B.idx->k, z.p, rg.as<hymet_mm_reg>(), wv.as<int32_t>(), cov.as<uint64_t>(),
-                          tmp.as<int32_t>(), nr.as<int32_t>(), C.n_anchor, NC, B.NM, C.cq.as<uint32_t>(),
-                          B.pos_tab.as<MiniWord>(), B.d_qbase.as<int64_t>(), skip_q, sumk.as<uint64_t>(),
-                          std::exchange(sumk_done, true));
+                          tmp.as<int32_t>(), nr.as<int32_t>(), C.n_anchor, NC, C.cq.as<uint32_t>(),
+                          B.pos_tab.as<MiniWord>(), B.d_qbase.as<int64_t>(), skip_q);
 }
 
 // one chain set's region records: where reg_gather_kernel reads a query's regions from
@@ -1093,14 +1090,12 @@ static int mm_map_impl(hymet_ctx *ctx, const hymet_mm_index *idx, const hymet_mm
     tr.mark("long join");
     // -------------------------------------------------------------- 8 regions
     // region records stay in HBM: per chain set, records at the set's chain offsets + counts
-    DevBuf sumk, rg1, nr1, rg2, nr2;
-    HY_HIP(sumk.alloc(8 * (size_t)(n_q + 1), ctx->stream));
-    bool sumk_done = false;
+    DevBuf rg1, nr1, rg2, nr2;
     const uint32_t *fl = joined ? flag.as<uint32_t>() : nullptr;
-    rc = run_regions(B, C1, rg1, nr1, fl, sumk, sumk_done);
+    rc = run_regions(B, C1, rg1, nr1, fl);
     if (rc) return rc;
     if (joined) {
-        rc = run_regions(B, C2, rg2, nr2, nullptr, sumk, sumk_done);
+        rc = run_regions(B, C2, rg2, nr2, nullptr);
         if (rc) return rc;
     }
     const RegSet r1{nr1.as<int32_t>(), C1.d_qc.as<int64_t>(), rg1.as<hymet_mm_reg>()};

@@ -2,12 +2,14 @@
 // mm_gen_regs (score + hash order), mm_reg_set_coor / mm_cal_fuzzy_len, mm_set_parent,
 // mm_select_sub (+ mm_sync_regs), mm_est_err, mm_filter_strand_retained, mm_set_mapq.
 // Everything that walks a chain's anchors is anchor-parallel and runs first:
+//   chain_rec_kernel        one thread per chain: a packed record of what the next kernel needs
+//                           of a chain and its query, the accumulators' start values;
 //   chain_stats_flat_kernel two chained anchors per thread: mlen/blen terms (mm_reg_set_coor),
 //                           its minimizer index (mm_est_err's get_mini_idx, by table lookup)
 //                           and the first anchor, in est_err's walking order, whose index does
 //                           not increase -- est_err's sequential two-pointer walk matches
-//                           exactly the prefix before it; segmented per chain;
-//   query_sumk_kernel       one wave per query: sum of minimizer spans (avg_k).
+//                           exactly the prefix before it; segmented per chain.
+// (est_err's avg_k needs no pass: every seeded minimizer's span is the index's k.)
 // regions_kernel then runs one thread per query: a query has few chains (tens) and every step
 // left is an O(n^2)-at-most scan over them.  Scratch lives in global memory at the query's
 // chain range.  Float/double arithmetic is written in the order of hit.c (-ffp-contract=off).
@@ -68,8 +70,7 @@ struct RegParams {
     const int64_t *cboff;          // chain -> offset of its anchors in chain order (region `as`)
     const int64_t *qc;             // n_q + 1 chain offsets
     const int64_t *qb;             // n_q + 1 anchor offsets
-    const uint64_t *mini_pos;
-    const int64_t *mp_off;         // n_q + 1
+    const int64_t *mp_off;         // n_q + 1 offsets of the queries' seeded minimizers
     const int64_t *qlen;
     const uint32_t *name_hash;
     const int32_t *rep_len;
@@ -86,7 +87,6 @@ struct RegParams {
     int32_t *n_regs;
     // per-chain anchor statistics (chain_stats_flat_kernel)
     const int32_t *c_mlen, *c_blen, *c_st, *c_last, *c_fv;
-    const uint64_t *q_sumk;
     const uint32_t *skip_q;        // queries whose regions come from the long join (nullable)
     int wave_min;                  // queries of more chains than this take regions_wave_kernel
     int lds_max;                   // ... and hold their regions in LDS up to this many (kRegSmall)
@@ -113,20 +113,15 @@ __device__ void set_coor(hymet_mm_reg *r, int32_t qlen, uint64_t x0, uint32_t y0
 }
 
 struct AnchorStatParams {
-    const uint64_t *ax, *cu;
+    const uint32_t *ax32;         // x's low word (the strand comes from the chain's record)
     const uint32_t *ay;           // y's low word
     int span;                     // y's high word, the set's constant
     const int32_t *ids;           // backtrack output (chains end -> start)
-    const int64_t *cfirst;        // each chain's first slot in it
-    const int64_t *cboff, *qb, *qlen, *mp_off;
-    const uint64_t *mini_pos;
+    const int64_t *cboff;         // chain -> offset of its anchors in chain order (the fallback's search)
     int64_t NB, NC;
-    int n_q;
-    const uint32_t *cq;      // query of each chain
-    int32_t *c_mlen, *c_blen, *c_st, *c_last;
+    int32_t *c_mlen, *c_blen, *c_st, *c_last, *c_fv;
     const MiniWord *mtab;    // query base -> minimizer index (or -1): word (qbase[q] + position) >> 6
-    const int64_t *qbase;
-    const uint32_t *skip_q;  // queries whose chains are superseded by the long join (nullable)
+    int stage;               // chain records a block stages in LDS (kStatStage; HYMET_STAT_STAGE in tests)
 };
 
 // Per-chain anchor statistics, flat over the chained anchors in chain order (position b of
@@ -139,158 +134,209 @@ struct AnchorStatParams {
 // minimizer, stalls it to the end).  The minimizer index (get_mini_idx) is one 16-byte load
 // from a position -> index table (MiniWord: start bits and a base index per 64 query bases,
 // -1 where no seeded minimizer starts; built by mini_bits/base_kernel in hymet_mm_map).  Each block finds its
-// lanes' chains by a search over the next 256 chain offsets staged in LDS; neighbours in
-// chain order come from the adjacent lanes (a load only at a wave edge); then a segmented
-// wave reduction by chain and one atomic per chain piece in the wave.  c_mlen / c_blen
-// start at 0, c_fv at INT32_MAX (every anchor offers cnt).
-__device__ __forceinline__ int32_t mini_idx_at(const AnchorStatParams &P, int64_t q, int qlen, uint64_t ax, uint32_t ay) {
-    int32_t x = (int32_t)ay;
-    if (ax >> 63) x = qlen - 1 - (int32_t)ay + P.span - 1;
-    return (x >= 0 && x < qlen) ? mini_word_idx(P.mtab[(P.qbase[q] + x) >> 6], x) : -1;
-}
+// lanes' chains by a search over the records of the next chains staged in LDS; neighbours in
+// chain order come from the adjacent lanes, and at a wave's two edges from halo positions
+// that the edge lanes load beside their own; then a segmented wave reduction by chain and
+// one atomic per chain piece in the wave.  c_mlen / c_blen start at 0, c_fv at INT32_MAX
+// (every anchor offers cnt).
 
 // chain_stats_flat_kernel: kStatItems chain-order positions per thread (rows of 256 in a
 // block), their loads issued row after row before any is used -- one position per thread
-// left every thread waiting on a chain of ~6 dependent loads (chain, query, chain slot,
-// anchor, minimizer index) with nothing else in flight.  Two per thread: C4 one-stream
-// 108.6 ms per step at four, 86.6 at two, 196.5 at eight (the register-held rows cost
-// occupancy; profiles/r05_chain_stats/)
+// left every thread waiting on a chain of dependent loads with nothing else in flight.
+// Two per thread: C4 one-stream 108.6 ms per step at four, 86.6 at two, 196.5 at eight (the
+// register-held rows cost occupancy; profiles/r05_chain_stats/)
 #ifndef HYMET_STAT_ITEMS
 #define HYMET_STAT_ITEMS 2
 #endif
 constexpr int kStatItems = HYMET_STAT_ITEMS;
 constexpr int kStatSpan = 256 * kStatItems;  // chain-order positions per block
+constexpr int kStatStage = 256;              // chain records a block stages in LDS (one per thread)
 
-// the chain holding chain-order position kStatSpan b, for every block b of
-// chain_stats_flat_kernel (one thread per chain writes the block starts inside it: no
-// per-block binary search, whose ~log2(NC) dependent loads held the whole block)
-__global__ void block_chain_kernel(const int64_t *cboff, int64_t NC, int64_t NB, int32_t *blk_c0) {
+// What chain_stats_flat_kernel needs of a chain, in one 32-byte record: a position's chain
+// and query fields are one LDS read (one uniform load in a block inside one chain), where
+// they were three dependent gathers (chain offsets, chain fields, query fields).
+struct __attribute__((aligned(16))) ChainRec {
+    int32_t cboff;   // offset of the chain's anchors in chain order (NB < 2^31: 32-bit chain links)
+    int32_t f0;      // cfirst + cnt - 1: the slot in ids of its chain-order position 0
+    int32_t cnt;
+    uint32_t q;
+    int32_t qlen;
+    uint32_t flags;  // bit 0: reverse strand (bit 63 of its first anchor's x), bit 1: skip_q[q]
+    int64_t qbase;
+};
+static_assert(sizeof(ChainRec) == 32, "ChainRec is two 16-byte words");
+
+struct ChainRecParams {
+    const uint64_t *ax, *cu;
+    const int32_t *ids;
+    const int64_t *cfirst, *cboff, *qlen, *qbase;
+    const uint32_t *cq, *skip_q;  // skip_q: queries whose chains are superseded by the long join (nullable)
+    int64_t NB, NC;
+    ChainRec *rec;
+    int32_t *blk_c0;  // per block of chain_stats_flat_kernel: the chain holding its first position,
+                      // bit 31 set where that chain holds the whole block
+    int32_t *c_mlen, *c_blen, *c_fv;
+};
+
+// one thread per chain: its record, its accumulators' start values (mlen = blen = 0, first
+// stall = 0x7f7f7f7f: every anchor offers cnt) and the stats blocks that start inside it (no per-block
+// binary search, whose ~log2(NC) dependent loads held the whole block)
+__global__ void chain_rec_kernel(ChainRecParams P) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= NC) return;
-    const int64_t s = cboff[c], e = c + 1 < NC ? cboff[c + 1] : NB;
-    for (int64_t b = (s + kStatSpan - 1) / kStatSpan; b * kStatSpan < e; ++b) blk_c0[b] = (int32_t)c;
+    if (c > P.NC) return;
+    P.c_mlen[c] = 0, P.c_blen[c] = 0, P.c_fv[c] = 0x7f7f7f7f;
+    if (c == P.NC) return;
+    const int64_t s = P.cboff[c], e = c + 1 < P.NC ? P.cboff[c + 1] : P.NB;
+    const int32_t cnt = (int32_t)P.cu[c];
+    const int64_t f0 = P.cfirst[c] + cnt - 1;
+    const uint32_t q = P.cq[c];
+    ChainRec r;
+    r.cboff = (int32_t)s, r.f0 = (int32_t)f0, r.cnt = cnt, r.q = q;
+    r.qlen = (int32_t)P.qlen[q];
+    r.flags = (uint32_t)(P.ax[P.ids[f0]] >> 63) | (P.skip_q && P.skip_q[q] ? 2u : 0u);
+    r.qbase = P.qbase[q];
+    P.rec[c] = r;
+    for (int64_t b = (s + kStatSpan - 1) / kStatSpan; b * kStatSpan < e; ++b)
+        P.blk_c0[b] = (int32_t)c | ((b + 1) * kStatSpan <= e || c + 1 == P.NC ? INT32_MIN : 0);
 }
 
-__global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams P, const int32_t *blk_c0, int32_t *c_fv) {
+// a chain anchor's position on the query's forward strand (get_mini_idx), clamped into the
+// query; *inq: it was inside
+__device__ __forceinline__ int32_t stat_qpos(uint32_t y, bool rev, int32_t qlen, int32_t span, bool *inq) {
+    const int32_t xq = rev ? qlen - 1 - (int32_t)y + span - 1 : (int32_t)y;
+    *inq = xq >= 0 && xq < qlen;
+    return *inq ? xq : 0;
+}
+
+__global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams P, const ChainRec *rec, const int32_t *blk_c0) {
     constexpr int K = kStatItems;
-    __shared__ int32_t s_st[kStatSpan + 1];  // block-relative starts of chains c0 .. c0 + kStatSpan (clamped)
+    __shared__ int4 s_rec[2 * kStatStage];  // records of chains c0 .. c0 + stage - 1
+    __shared__ int32_t s_st[kStatStage];    // their block-relative starts (clamped; kStatSpan beyond the last chain)
+    const int4 *rec4 = reinterpret_cast<const int4 *>(rec);
     const int64_t b0 = (int64_t)blockIdx.x * kStatSpan;
-    const int64_t cb0 = blk_c0[blockIdx.x];  // last c with cboff[c] <= b0
-    for (int i = threadIdx.x; i <= kStatSpan; i += blockDim.x) {
-        const int64_t cc = cb0 + i;
-        s_st[i] = cc < P.NC ? (int32_t)min(P.cboff[cc] - b0, (int64_t)kStatSpan) : kStatSpan;
-    }
-    __syncthreads();
+    const int32_t bw = blk_c0[blockIdx.x];
+    // a block inside one chain (long chains: most blocks) skips the staging and the searches
+    // and sums its statistics over the block
+    const bool one_chain = bw < 0;
+    const int32_t cb0 = bw & INT32_MAX;  // last c with cboff[c] <= b0
     const int lane = threadIdx.x & 63;
-    int64_t c[K], q[K], f0[K];  // chain, query, slot of chain-order position 0 in ids
-    bool act[K];
-    int32_t cnt[K], j[K], qlen[K], cur[K];
-    uint64_t x[K];
-    uint32_t y[K];
-    // a block inside one chain (long chains: most blocks) skips the searches and sums its
-    // statistics over the block
-    const bool one_chain = s_st[1] >= kStatSpan;
-    int32_t t_dm = 0, t_db = 0, t_fv = INT32_MAX;
-    int64_t qb[K];
+    const bool edge = lane == 0 || lane == 63;
+    int4 ra[K], rb[K];  // the position's chain record
+    int32_t ci[K];      // its chain (-1: no position)
     if (one_chain) {
-        // the block's one chain: its values are block-uniform (scalar loads), every position's
-        // anchor one slot further down the chain
-        const int64_t qq = (int64_t)P.cq[cb0];
-        const int32_t cn = (int32_t)P.cu[cb0];
-        const int64_t cbs = P.cboff[cb0], f00 = P.cfirst[cb0] + cn - 1;
-        const int ql = (int)P.qlen[qq];
-        const int64_t qbb = P.qbase[qq];
-        const bool sk = P.skip_q && P.skip_q[qq];
+        // the block's one chain: its record is block-uniform, every position's anchor one slot
+        // further down the chain
+        const int4 a = rec4[2 * (int64_t)cb0], b = rec4[2 * (int64_t)cb0 + 1];
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            const int64_t b = b0 + 256 * k + threadIdx.x;
-            c[k] = b < P.NB ? cb0 : -1;
-            q[k] = qq, cnt[k] = cn, f0[k] = f00, qlen[k] = ql, qb[k] = qbb;
-            act[k] = b < P.NB && !sk;
-            j[k] = act[k] ? (int32_t)(b - cbs) : 0;
+            ra[k] = a, rb[k] = b;
+            ci[k] = b0 + 256 * k + threadIdx.x < P.NB ? cb0 : -1;
         }
     } else {
+        const int S = P.stage;
+        for (int i = threadIdx.x; i < S; i += blockDim.x) {
+            const int64_t cc = (int64_t)cb0 + i;
+            const int64_t cl = cc < P.NC ? cc : P.NC - 1;
+            const int4 a = rec4[2 * cl];
+            s_rec[2 * i] = a, s_rec[2 * i + 1] = rec4[2 * cl + 1];
+            s_st[i] = cc < P.NC ? (int32_t)min((int64_t)a.x - b0, (int64_t)kStatSpan) : kStatSpan;
+        }
+        __syncthreads();
 #pragma unroll
         for (int k = 0; k < K; k++) {
             const int r = 256 * k + (int)threadIdx.x;  // block-relative position
             const int64_t b = b0 + r;
-            c[k] = -1;
+            ci[k] = -1;
+            int lo = 0;
             if (b < P.NB) {
-                int lo = 0, hi = kStatSpan;  // last i with s_st[i] <= r (s_st[0] <= 0, nondecreasing)
+                int hi = S - 1;  // last i with s_st[i] <= r (s_st[0] <= 0, nondecreasing)
                 while (lo < hi) {
                     const int mid = (lo + hi + 1) >> 1;
                     if (s_st[mid] <= r) lo = mid;
                     else hi = mid - 1;
                 }
-                c[k] = cb0 + lo;
-                if (lo == kStatSpan) {  // beyond the staged chains (chains with no anchors in the range)
-                    int64_t l2 = c[k], h2 = P.NC - 1;
-                    while (l2 < h2) {
-                        const int64_t mid = (l2 + h2 + 1) >> 1;
-                        if (P.cboff[mid] <= b) l2 = mid;
-                        else h2 = mid - 1;
-                    }
-                    c[k] = l2;
+                ci[k] = cb0 + lo;
+            }
+            if (b < P.NB && lo == S - 1) {
+                // at or beyond the last staged chain (a run of chains with no anchors in the
+                // range, the chains of re-chained queries): search the chain offsets
+                int64_t l2 = ci[k], h2 = P.NC - 1;
+                while (l2 < h2) {
+                    const int64_t mid = (l2 + h2 + 1) >> 1;
+                    if (P.cboff[mid] <= b) l2 = mid;
+                    else h2 = mid - 1;
                 }
+                ci[k] = (int32_t)l2;
+                ra[k] = rec4[2 * l2], rb[k] = rec4[2 * l2 + 1];
+            } else {
+                ra[k] = s_rec[2 * lo], rb[k] = s_rec[2 * lo + 1];  // (no position: chain c0's, valid indices)
             }
         }
-        // (every load below is unconditional, at a valid index for inactive positions -- chain 0,
-        // its first slot -- so the rows' loads stay straight-line code and are all in flight
-        // before the first is used)
-#pragma unroll
-        for (int k = 0; k < K; k++) q[k] = (int64_t)P.cq[c[k] >= 0 ? c[k] : 0];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const int64_t cc = c[k] >= 0 ? c[k] : 0;
-            cnt[k] = (int32_t)P.cu[cc];
-            const int64_t cb = P.cboff[cc];
-            f0[k] = P.cfirst[cc] + cnt[k] - 1;
-            j[k] = (int32_t)(b0 + 256 * k + threadIdx.x - cb);
-            qlen[k] = (int)P.qlen[q[k]];
-            qb[k] = P.qbase[q[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            act[k] = c[k] >= 0;
-            if (P.skip_q) act[k] = act[k] && !P.skip_q[q[k]];
-            if (!act[k]) j[k] = 0;
-        }
     }
+    // (every load below is at a valid index for a thread without a position -- its record's
+    // chain, first slot -- so the rows' loads stay straight-line code and are all in flight
+    // before the first is used.  The wave's edge lanes load a halo position beside their own:
+    // lane 0 the chain-order position below it, lane 63 the one above, both used only where
+    // they lie in the lane's own chain -- so they share its record -- and clamped into it)
+    bool act[K], rev[K];
+    int32_t cnt[K], j[K], f0[K], qlen[K], cur[K];
+    int64_t qb[K];
+    int32_t a[K], ah[K], hcur[K];
+    uint32_t x[K], y[K], hx[K], hy[K];
+    MiniWord mw[K], mh[K];
+    int32_t xc[K], xh[K];
+    bool inq[K], inh[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        const int64_t a = P.ids[f0[k] - j[k]];
-        x[k] = P.ax[a], y[k] = P.ay[a];
+        cnt[k] = ra[k].z, f0[k] = ra[k].y, qlen[k] = rb[k].x;
+        qb[k] = (int64_t)((uint64_t)(uint32_t)rb[k].w << 32 | (uint32_t)rb[k].z);
+        rev[k] = rb[k].y & 1;
+        act[k] = ci[k] >= 0 && !(rb[k].y & 2);
+        j[k] = act[k] ? (int32_t)(b0 + 256 * k + threadIdx.x - ra[k].x) : 0;
+        ah[k] = 0, hx[k] = 0, hy[k] = 0, xh[k] = 0, inh[k] = false, hcur[k] = -1;
     }
 #pragma unroll
-    for (int k = 0; k < K; k++) {  // mini_idx_at, its table read unconditional
-        int32_t xq = (int32_t)y[k];
-        if (x[k] >> 63) xq = qlen[k] - 1 - (int32_t)y[k] + P.span - 1;
-        const bool inq = xq >= 0 && xq < qlen[k];
-        const int32_t xc = inq ? xq : 0;
-        const int32_t v = mini_word_idx(P.mtab[(qb[k] + xc) >> 6], xc);
-        cur[k] = act[k] && inq ? v : -1;
+    for (int k = 0; k < K; k++) a[k] = P.ids[f0[k] - j[k]];
+    if (edge) {
+#pragma unroll
+        for (int k = 0; k < K; k++) ah[k] = P.ids[f0[k] - (lane == 0 ? max(j[k] - 1, 0) : min(j[k] + 1, cnt[k] - 1))];
     }
+#pragma unroll
+    for (int k = 0; k < K; k++) x[k] = P.ax32[a[k]], y[k] = P.ay[a[k]];
+    if (edge) {
+#pragma unroll
+        for (int k = 0; k < K; k++) hx[k] = P.ax32[ah[k]], hy[k] = P.ay[ah[k]];
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) {  // get_mini_idx, its table read unconditional
+        xc[k] = stat_qpos(y[k], rev[k], qlen[k], P.span, &inq[k]);
+        mw[k] = P.mtab[(qb[k] + xc[k]) >> 6];
+    }
+    if (edge) {
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            xh[k] = stat_qpos(hy[k], rev[k], qlen[k], P.span, &inh[k]);
+            mh[k] = P.mtab[(qb[k] + xh[k]) >> 6];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) cur[k] = act[k] && inq[k] ? mini_word_idx(mw[k], xc[k]) : -1;
+    if (edge) {
+#pragma unroll
+        for (int k = 0; k < K; k++) hcur[k] = inh[k] ? mini_word_idx(mh[k], xh[k]) : -1;
+    }
+    int32_t t_dm = 0, t_db = 0, t_fv = INT32_MAX;
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        // chain-order neighbours (anchor and minimizer index) from the adjacent lanes (same
-        // chain), else loaded
-        const int32_t ci = (int32_t)c[k];
-        const int32_t cprev = __shfl_up(ci, 1, 64), cnext = __shfl_down(ci, 1, 64);
-        uint64_t xp = __shfl_up(x[k], 1, 64), xn = __shfl_down(x[k], 1, 64);
-        uint32_t yp = __shfl_up(y[k], 1, 64), yn = __shfl_down(y[k], 1, 64);
-        const int32_t cur_p = __shfl_up(cur[k], 1, 64), cur_n = __shfl_down(cur[k], 1, 64);
+        // chain-order neighbours (anchor and minimizer index): the adjacent lanes, at the
+        // wave's edges the halo.  Position b - 1 is in this chain iff j > 0, b + 1 iff
+        // j + 1 < cnt; a neighbour of another chain is not used
+        uint32_t xp = __shfl_up(x[k], 1, 64), yp = __shfl_up(y[k], 1, 64);
+        int32_t cur_p = __shfl_up(cur[k], 1, 64), cur_n = __shfl_down(cur[k], 1, 64);
+        if (lane == 0) xp = hx[k], yp = hy[k], cur_p = hcur[k];
+        if (lane == 63) cur_n = hcur[k];
         int dm = 0, db = 0, fv = INT32_MAX;
         if (act[k]) {
-            const bool rev = x[k] >> 63;
-            const bool own_p = lane > 0 && cprev == ci, own_n = lane < 63 && cnext == ci;
-            if (j[k] > 0 && !own_p) {
-                const int64_t a = P.ids[f0[k] - j[k] + 1];
-                xp = P.ax[a], yp = P.ay[a];
-            }
-            if (rev && j[k] + 1 < cnt[k] && !own_n) {
-                const int64_t a = P.ids[f0[k] - j[k] - 1];
-                xn = P.ax[a], yn = P.ay[a];
-            }
             const int32_t span = P.span;
             if (j[k] == 0) {
                 dm = db = span;
@@ -300,21 +346,20 @@ __global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams 
                 db = tl > ql ? tl : ql;
                 dm = tl > span && ql > span ? span : tl < ql ? tl : ql;
             }
-            const int32_t kk = rev ? cnt[k] - 1 - j[k] : j[k];  // est_err walking order
+            const int32_t kk = rev[k] ? cnt[k] - 1 - j[k] : j[k];  // est_err walking order
             fv = cnt[k];
             if (kk >= 1) {
-                const int32_t prev = rev ? (own_n ? cur_n : mini_idx_at(P, q[k], qlen[k], xn, yn))
-                                         : (own_p ? cur_p : mini_idx_at(P, q[k], qlen[k], xp, yp));
+                const int32_t prev = rev[k] ? cur_n : cur_p;
                 if (cur[k] < 0 || cur[k] <= prev) fv = kk;
             }
-            if (kk == 0) P.c_st[c[k]] = cur[k];
-            if (kk == cnt[k] - 1) P.c_last[c[k]] = cur[k];
+            if (kk == 0) P.c_st[ci[k]] = cur[k];
+            if (kk == cnt[k] - 1) P.c_last[ci[k]] = cur[k];
         }
         if (one_chain) {  // summed over the block below: one atomic per block and counter
             t_dm += dm, t_db += db, t_fv = min(t_fv, fv);
             continue;
         }
-        const int32_t cr = act[k] ? ci : -1;
+        const int32_t cr = act[k] ? ci[k] : -1;
         // segmented inclusive reduction over lanes of the same chain (contiguous in the wave)
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -324,9 +369,9 @@ __global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams 
         }
         const int32_t cn = __shfl_down(cr, 1, 64);
         if (act[k] && (lane == 63 || cn != cr)) {  // last lane of its chain piece in this wave
-            atomicAdd(P.c_mlen + c[k], dm);
-            atomicAdd(P.c_blen + c[k], db);
-            atomicMin(c_fv + c[k], fv);
+            atomicAdd(P.c_mlen + ci[k], dm);
+            atomicAdd(P.c_blen + ci[k], db);
+            atomicMin(P.c_fv + ci[k], fv);
         }
     }
     if (one_chain) {
@@ -345,26 +390,8 @@ __global__ __launch_bounds__(256) void chain_stats_flat_kernel(AnchorStatParams 
         if (threadIdx.x == 0 && act[0]) {  // (a skipped query's chain: no update, as per lane)
             atomicAdd(P.c_mlen + cb0, r_dm[0] + r_dm[1] + r_dm[2] + r_dm[3]);
             atomicAdd(P.c_blen + cb0, r_db[0] + r_db[1] + r_db[2] + r_db[3]);
-            atomicMin(c_fv + cb0, min(min(r_fv[0], r_fv[1]), min(r_fv[2], r_fv[3])));
+            atomicMin(P.c_fv + cb0, min(min(r_fv[0], r_fv[1]), min(r_fv[2], r_fv[3])));
         }
-    }
-}
-
-// one wave per query: sum of minimizer spans (avg_k)
-__global__ __launch_bounds__(64) void query_sumk_kernel(const uint64_t *mini_pos, const int64_t *mp_off, int n_q,
-                                                        unsigned long long *sumk) {
-    for (int q = blockIdx.x; q < n_q; q += gridDim.x) {
-        unsigned long long sk = 0;
-        const int64_t m1 = mp_off[q + 1];
-        for (int64_t m = mp_off[q] + threadIdx.x; m < m1; m += 256) {  // 4 loads in flight per lane
-            uint64_t v[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = m + 64 * j < m1 ? mini_pos[m + 64 * j] : 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) sk += v[j] >> 32 & 0xff;
-        }
-        for (int o = 32; o > 0; o >>= 1) sk += __shfl_xor(sk, o, 64);
-        if (threadIdx.x == 0) sumk[q] = sk;
     }
 }
 
@@ -526,7 +553,7 @@ __device__ void regions_seq(const RegParams &P, int q) {
         const int64_t m0 = P.mp_off[q];
         const int32_t nm = (int32_t)(P.mp_off[q + 1] - m0);
         if (nm > 0) {
-            const uint64_t sum_k = P.q_sumk[q];
+            const uint64_t sum_k = (uint64_t)P.span * (uint64_t)nm;  // every minimizer's span is the set's
             const float avg_k = __fdiv_rn((float)sum_k, (float)nm);
             for (int i = 0; i < n; ++i) {
                 hymet_mm_reg *ri = &r[i];
@@ -1057,7 +1084,7 @@ __device__ __forceinline__ void regions_wave(const RegParams &P, int q, unsigned
         const int64_t m0 = P.mp_off[q];
         const int32_t nm = (int32_t)(P.mp_off[q + 1] - m0);
         if (nm > 0) {
-            const uint64_t sum_k = P.q_sumk[q];
+            const uint64_t sum_k = (uint64_t)P.span * (uint64_t)nm;  // every minimizer's span is the set's
             const float avg_k = __fdiv_rn((float)sum_k, (float)nm);
             for (int i = lane; i < n; i += 64) {
                 hymet_mm_reg *ri = &r[i];
@@ -1147,54 +1174,46 @@ __device__ __forceinline__ void regions_wave(const RegParams &P, int q, unsigned
     if (lane == 0) P.n_regs[q] = n;
 }
 
-// per-chain stats accumulators: mlen = blen = 0, first-anchor minimum = 0x7f7f7f7f
-__global__ void chain_stats_init_kernel(int32_t *c_mlen, int32_t *c_blen, int32_t *c_fv, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) c_mlen[i] = 0, c_blen[i] = 0, c_fv[i] = 0x7f7f7f7f;
-}
-
 }  // namespace
 
-int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint32_t *ay, int span, const int32_t *ids, const int64_t *cfirst,
-                   const uint64_t *cu, const int64_t *cboff,
-                   const int64_t *qc, const int64_t *qb, const uint64_t *mini_pos, const int64_t *mp_off, const int64_t *qlen,
+int launch_regions(hymet_ctx *ctx, const uint64_t *ax, const uint32_t *ax32, const uint32_t *ay, int span, const int32_t *ids,
+                   const int64_t *cfirst, const uint64_t *cu, const int64_t *cboff,
+                   const int64_t *qc, const int64_t *qb, const int64_t *mp_off, const int64_t *qlen,
                    const uint32_t *name_hash, const int32_t *rep_len, const int64_t *ref_len, int n_q, const hymet_mm_opt *o,
                    int k, void *z, hymet_mm_reg *regs, int32_t *w, uint64_t *cov, int32_t *tmp, int32_t *n_regs,
-                   int64_t NB, int64_t NC, int64_t NM, const uint32_t *cq,
-                   const MiniWord *mtab, const int64_t *qbase, const uint32_t *skip_q, uint64_t *sumk, bool sumk_done) {
+                   int64_t NB, int64_t NC, const uint32_t *cq,
+                   const MiniWord *mtab, const int64_t *qbase, const uint32_t *skip_q) {
     if (n_q <= 0) return HYMET_OK;
     hipStream_t st = ctx->stream;
-    DevBuf cst, blk;
+    DevBuf cst, blk, rec;
     HY_HIP(cst.alloc(4 * 5 * (size_t)(NC + 1), st));
     int32_t *c_mlen = cst.as<int32_t>(), *c_blen = c_mlen + (NC + 1), *c_st = c_blen + (NC + 1), *c_last = c_st + (NC + 1),
             *c_fv = c_last + (NC + 1);
     {
-        // chain slot (4) + anchor x, y (8 + 4) + its minimizer-table read (4: 16 B per 64 bases) per chained anchor
-        ProfScope _ps(ctx, "mm_chain_stats", (double)NB * (4.0 + 12.0 + 4.0) + (double)NM * 8.0);
-        AnchorStatParams A{ax, cu, ay, span, ids, cfirst, cboff, qb, qlen, mp_off, mini_pos, NB, NC, n_q, cq,
-                           c_mlen, c_blen, c_st, c_last, mtab, qbase, skip_q};
+        // chain slot (4) + anchor x, y low words (4 + 4) + its minimizer-table read (4: 16 B per 64
+        // bases) per chained anchor; a 32-byte record per chain written, read back by the blocks
+        // that stage it, and its accumulators' start values
+        ProfScope _ps(ctx, "mm_chain_stats", (double)NB * (4.0 + 8.0 + 4.0) + (double)NC * (2.0 * sizeof(ChainRec) + 12.0));
         if (NB > 0) {
-            hipLaunchKernelGGL(chain_stats_init_kernel, dim3((unsigned)cdiv(NC + 1, 256)), dim3(256), 0, st, c_mlen, c_blen,
-                               c_fv, NC + 1);
-            HY_CHECK_LAUNCH("chain_stats_init_kernel");
+            HY_ARG(ax32 != nullptr, "launch_regions: the chained anchor set has no x low words");
+            HY_HIP(rec.alloc(sizeof(ChainRec) * (size_t)(NC + 1), st));
             HY_HIP(blk.alloc(4 * (size_t)(cdiv(NB, kStatSpan) + 1), st));
-            hipLaunchKernelGGL(block_chain_kernel, dim3((unsigned)cdiv(NC, 256)), dim3(256), 0, st, cboff, NC, NB,
-                               blk.as<int32_t>());
-            HY_CHECK_LAUNCH("block_chain_kernel");
+            const ChainRecParams R{ax, cu, ids, cfirst, cboff, qlen, qbase, cq, skip_q, NB, NC, rec.as<ChainRec>(),
+                                   blk.as<int32_t>(), c_mlen, c_blen, c_fv};
+            hipLaunchKernelGGL(chain_rec_kernel, dim3((unsigned)cdiv(NC + 1, 256)), dim3(256), 0, st, R);
+            HY_CHECK_LAUNCH("chain_rec_kernel");
+            // HYMET_STAT_STAGE (tests): stage that many chain records per block, so a handful of
+            // chains reaches the search beyond the staged ones
+            const AnchorStatParams A{ax32, ay, span, ids, cboff, NB, NC, c_mlen, c_blen, c_st, c_last, c_fv, mtab,
+                                     (int)env_int("HYMET_STAT_STAGE", kStatStage, 1, kStatStage)};
             hipLaunchKernelGGL(chain_stats_flat_kernel, dim3((unsigned)cdiv(NB, kStatSpan)), dim3(256), 0, st, A,
-                               (const int32_t *)blk.as<int32_t>(), c_fv);
+                               (const ChainRec *)rec.as<ChainRec>(), (const int32_t *)blk.as<int32_t>());
             HY_CHECK_LAUNCH("chain_stats_flat_kernel");
         }
-        if (!sumk_done) {  // per query, shared by the batch's two chain sets
-            const int nqb = n_q < ctx->n_cu * 64 ? n_q : ctx->n_cu * 64;
-            hipLaunchKernelGGL(query_sumk_kernel, dim3((unsigned)nqb), dim3(64), 0, st, mini_pos, mp_off, n_q,
-                               (unsigned long long *)sumk);
-            HY_CHECK_LAUNCH("query_sumk_kernel");
-        }
     }
-    RegParams P{ax, ay, span, ids, cfirst, cu, cboff, qc, qb, mini_pos, mp_off, qlen, name_hash, rep_len, ref_len, n_q, o->seed, k,
+    RegParams P{ax, ay, span, ids, cfirst, cu, cboff, qc, qb, mp_off, qlen, name_hash, rep_len, ref_len, n_q, o->seed, k,
                 o->mask_level, o->pri_ratio, o->mask_len, o->best_n, o->max_gap, o->min_chain_score, (U128 *)z, regs, w, cov,
-                tmp, n_regs, c_mlen, c_blen, c_st, c_last, c_fv, sumk, skip_q, kRegWave, kRegSmall, nullptr, 64};
+                tmp, n_regs, c_mlen, c_blen, c_st, c_last, c_fv, skip_q, kRegWave, kRegSmall, nullptr, 64};
     // tests / A-B: HYMET_REG_WAVE (chains above which a query takes the wave kernel),
     // HYMET_REG_LDS (chains up to which the wave kernel works in LDS; 32: every wave query on the
     // global-scratch path from 33 chains: a query's share of that scratch, 2n entries, holds

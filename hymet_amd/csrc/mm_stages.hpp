@@ -83,6 +83,7 @@ struct ChainSet {
     DevBuf ids, cfirst;        // backtrack output (each chain end -> start) and each chain's first slot
     const uint64_t *ax = nullptr;  // the chained anchor set (alive as long as the chains)
     const uint32_t *ay = nullptr;
+    const uint32_t *ax32 = nullptr;  // its x low words (chain_set derives them where the set's writer left them out)
     int span = 0;
     DevBuf cq;              // query of each chain
     int64_t n_anchor = 0, n_chain = 0;
